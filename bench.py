@@ -25,6 +25,12 @@ N > 1 runs one process per GPU.  The driver launches it under
 the environment) starts that launcher as a child process before touching the
 GPU and relays rank 0's line.  Prints ONE JSON line on stdout (rank 0); every
 other byte any rank or library writes goes to stderr.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds
+the measurements the headline figure does not need (their fields are null
+without it): graph_build_ms, cold_layer_ms, roofline.traffic, the N > 1 link
+probe and cpu_baseline.  --dump-outputs DIR writes the last timed step's
+outputs as DIR/<name>.npy for comparing two builds on the same seeded inputs.
 """
 
 from __future__ import annotations
@@ -113,6 +119,27 @@ def pmc_step_traffic(name: str) -> tuple[float | None, str | None]:
         if ks and all(v.get("source_hash") == mod.kernel_source_hash(k) for k, v in ks.items()):
             return d["traffic_bytes_per_step"], str(path.relative_to(ROOT))
     return None, None
+
+
+DUMP_ROWS = 16384  # rows kept of a larger output: y and dx of a training step, 256 columns wide, stay under 64 MB
+
+
+def dump_outputs(out_dir: Path, outputs: dict, rank: int | None) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy (N > 1: <name>_r<rank>.npy), float32.
+    An array of more than DUMP_ROWS rows keeps DUMP_ROWS of them, drawn without replacement
+    from a generator seeded by the row count alone, in ascending order: the same rows in every
+    run and every build, so two dumps compare element for element."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.dim() and t.shape[0] > DUMP_ROWS:
+            rows = np.sort(np.random.default_rng(t.shape[0]).choice(t.shape[0], DUMP_ROWS, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(out_dir / (name + ("" if rank is None else f"_r{rank}") + ".npy"), t.float().cpu().numpy())
 
 
 def log(msg: str) -> None:
@@ -310,13 +337,22 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="ns", choices=sorted(CONFIGS))
     ap.add_argument("--exact", action="store_true", help="EXACT mode (no hub split)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-graph layer timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the warm "
+                         "graph rebuild (graph_build_ms), the cold-graph layer (cold_layer_ms), the committed PMC "
+                         "traffic (roofline.traffic), the N > 1 link probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32): y, and with --train "
+                         f"the gradients; an array of more than {DUMP_ROWS} rows is sampled at fixed seeded rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cold", action="store_true", help="with --full: skip the cold-graph layer timing")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--train", action="store_true",
                     help="a step is one training step: forward keeping the aggregate P, then backward "
                          "(dx over the transposed graph, dW = P^T dOut, db); GCN, one GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args.gpus))
@@ -376,12 +412,14 @@ def main() -> None:
         torch.cuda.synchronize()
         first_call_ms = (time.perf_counter() - t0) * 1e3
         g = next(reversed(kgx.graph._CACHE.values()))[1]
-        # steady-state graph preparation (CSR + schedule), timed warm: once per graph, not per step
-        t0 = time.perf_counter()
-        kgx.graph.build_csr(ei[0].contiguous(), ei[1].contiguous(), n_global, n_global,
-                            self_loops=kind in ("gcn", "gat"), gcn_norm=kind == "gcn", n_features=f_in)
-        torch.cuda.synchronize()
-        graph_build_ms = (time.perf_counter() - t0) * 1e3
+        graph_build_ms = None
+        if args.full:
+            # steady-state graph preparation (CSR + schedule), timed warm: once per graph, not per step
+            t0 = time.perf_counter()
+            kgx.graph.build_csr(ei[0].contiguous(), ei[1].contiguous(), n_global, n_global,
+                                self_loops=kind in ("gcn", "gat"), gcn_norm=kind == "gcn", n_features=f_in)
+            torch.cuda.synchronize()
+            graph_build_ms = (time.perf_counter() - t0) * 1e3
         e_agg, n_rows, max_deg = g.kept, g.n_dst, g.max_degree
 
         def step():  # the forward (inference) pass: no autograd state kept
@@ -396,7 +434,9 @@ def main() -> None:
             def step():  # one training step: forward (P kept), backward (dx, dW, db)
                 x.grad = None
                 layer.zero_grad(set_to_none=True)
-                layer([x, ei]).backward(gout)
+                y = layer([x, ei])
+                y.backward(gout)
+                return y
     else:
         from keras_geometric_amd.distributed import heartbeat
 
@@ -434,7 +474,8 @@ def main() -> None:
     split0 = kops.CU_SPLIT_LAUNCHES
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = None  # one step's output alive at a time, as when it was dropped on return
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -443,6 +484,12 @@ def main() -> None:
     events = kops.EVENT_SINK
     kops.EVENT_SINK = None
     cu_split = kops.CU_SPLIT_LAUNCHES > split0
+    if args.dump_outputs is not None:
+        grads = {"dx": x.grad, **{"d" + n.replace(".", "_"): p.grad for n, p in layer.named_parameters()}} \
+            if args.train else {}
+        dump_outputs(args.dump_outputs, {"y": out, **grads}, rank if world > 1 else None)
+        del grads
+    del out  # the buffers the --full legs free must have no holder left
     # aggregation-kernel time per step (N>1: own-source + halo launches, which overlap)
     kern_ms = sum(s.elapsed_time(e) for s, e in events) / args.steps
     launches = len(events) // args.steps
@@ -514,7 +561,7 @@ def main() -> None:
     mine = {"rank": rank, "e_agg": e_agg, "rows": n_rows, "ms_per_step": step_ms,
             "aggregation_ms": kern_ms, "launches_per_step": launches, "algorithmic_bytes": balg,
             "roofline_achieved_GBps": achieved, "roofline_frac": achieved / HBM_PEAK_GBS, **shard_info}
-    if world > 1:
+    if world > 1 and args.full:
         # every exchange step's pack-to-landing time (ShardedGraph.link_report), in a few extra
         # steps after the timed ones: the probe's timing events and stream waits cost ~3 % of a
         # step (tools/shard_sim.py --link-probe, profiles/r06/probe/), so they stay out of `value`
@@ -548,11 +595,11 @@ def main() -> None:
     ms_per_step = elapsed / args.steps * 1e3
     value = e_total * args.steps / elapsed
     traffic, traffic_src = (None, None)
-    if world == 1 and train_parts is None:
+    if args.full and world == 1 and train_parts is None:
         traffic, traffic_src = pmc_traffic(args.config, kernel)
-    elif world == 1 and kind == "gcn":
+    elif args.full and world == 1 and kind == "gcn":
         traffic, traffic_src = pmc_step_traffic(f"{args.config}_train")
-    if world == 1 and not args.train:
+    if args.full and world == 1 and not args.train:
         if not args.no_cold:
             # cold layer: CSR + (GCN) norm + schedule + forward from a fresh edge_index,
             # what the reference pays on every call (utils/main.py:8-33 per call)
@@ -640,8 +687,8 @@ def main() -> None:
                                  "exchange": shard_info.get("exchange"), "halo_chunks": shard_info.get("halo_chunks"),
                                  "merge_unit": shard_info.get("merge_unit"),
                                  "tuning_s": max((r.get("exchange_tuning_total_s") or 0.0) for r in ranks)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and kind == "gcn" and args.config != "tiny" \
-            and not args.train:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and kind == "gcn" \
+            and args.config != "tiny" and not args.train:
         log("timing the CPU baseline (oracle, C2-sized sample)")
         del x, layer, ei
         kgx.clear_cache()

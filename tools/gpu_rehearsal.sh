@@ -7,6 +7,6 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 for n in 2 4; do
   KGX_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --gpus $n --steps 3 --warmup 1 --config c2 \
+    --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --gpus $n --full --steps 3 --warmup 1 --config c2 \
     > gpurun_out/rehearsal$n.json 2> gpurun_out/rehearsal$n.err || exit $?
 done
