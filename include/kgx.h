@@ -480,6 +480,67 @@ int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_row
                        const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused segment softmax + weighted sum, the attention readouts' pooling (one
+ * pass over x, online softmax; plus a fix-up for split segments):
+ *   out[g,:] = sum_{i in g} softmax_g(s)_i * x[i,:]
+ *   softmax_g(s)_i = exp(s_i - m_g) / l_g,  m_g = max_{i in g} s_i,
+ *   l_g = sum_{i in g} exp(s_i - m_g)        (no epsilon in the denominator)
+ * Replaces ops.softmax(scores, axis=0) and ops.sum(weights * inputs, axis=0)
+ * of AttentionPooling (pooling/attention_pooling.py:409-412) and of every
+ * Set2Set processing step (:175-180, :206-211), per graph of a batch.
+ * Segments: a CSR rowptr[n_seg+1] over segment slots, `rows` (every segment,
+ * any order) and optionally the schedule items / split of kgx_schedule_build;
+ * with items == NULL each row of `rows` is reduced whole by one lane group.
+ * idx[slot] = node of a slot (a segment CSR's col), NULL = identity (sorted
+ * batches, the single graph rowptr = {0, N}).  x: [N, ld_x >= F], unit column
+ * stride.  Exactly one score source:
+ *   s [N]                      scores given, or
+ *   score_u [F], score_c [n_seg]   s_i = act(x_i . score_u + score_c[g]), act =
+ *     tanh with KGX_POOL_SCORE_TANH else identity, computed from the row just
+ *     loaded and stored to s_out [N] (Set2Set's Dense(1, tanh) over
+ *     concat(x, h): :165-172, with score_c[g] = h_g . k_h + b).
+ * Outputs: out [n_seg, ld_out >= F]; stats (optional) [n_seg, 2] = (m, l),
+ * kept for kgx_softmax_pool_backward.  partials: n_slots * (F + 2) floats when
+ * rows are split (per slot [F acc | m | l], merged in chunk order).
+ * A -inf score has weight 0; an empty segment is a zero row (the sum over no
+ * rows); a segment whose scores are all -inf, or that holds +inf or NaN, is
+ * NaN in its own row only (torch.softmax).  Numerator and denominator are
+ * accumulated in fp64; no atomics: the same bits on every run.
+ * F: 1 .. KGX_POOL_MAX_F (float4 lanes when F % 4 == 0 and x, out, score_u
+ * rows are 16-byte aligned, scalar lanes otherwise).
+ * Errors, before any device call: KGX_ERR_ARG for bad sizes, null pointers,
+ * both or neither score source, ld < F, split rows without split list and
+ * partials; KGX_ERR_UNSUPPORTED for F > KGX_POOL_MAX_F.
+ * ------------------------------------------------------------------------- */
+enum { KGX_POOL_SCORE_TANH = 1 };
+enum { KGX_POOL_MAX_F = 256 };
+int kgx_softmax_pool(const int32_t* rowptr, const int32_t* rows, int64_t n_seg,
+                     const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                     const int32_t* idx, const float* x, int64_t ld_x, int64_t F,
+                     const float* s, const float* score_u, const float* score_c, int flags, float* s_out,
+                     float* out, int64_t ld_out, float* stats, float* partials, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Backward of kgx_softmax_pool (autograd of the softmax / weighted sum of
+ * attention_pooling.py:175-180, :409-412).  Given G = d loss / d out [n_seg,
+ * ld_grad], the forward's out, stats and scores s (given, or its s_out):
+ *   alpha_i     = exp(s_i - m_g) / l_g
+ *   grad_x[i,:] = alpha_i * G[g,:]                       [N, ld_grad_x >= F]
+ *   grad_s[i]   = alpha_i * (x_i . G_g - out_g . G_g)    [N]
+ * in one pass over x.  seg [N]: the segment of every node, NULL = all nodes in
+ * segment 0; ids outside [0, n_seg) get zero gradient.  No schedule, partials
+ * or atomics.  grad_x is the pooled sum's part only: a fused score's chain
+ * (d tanh, score_u, score_c) is the caller's, from grad_s.
+ * Errors as kgx_softmax_pool: null pointers and ld < F are KGX_ERR_ARG,
+ * F > KGX_POOL_MAX_F is KGX_ERR_UNSUPPORTED, before any device call.
+ * ------------------------------------------------------------------------- */
+int kgx_softmax_pool_backward(int64_t N, int64_t n_seg, const int32_t* seg,
+                              const float* x, int64_t ld_x, int64_t F,
+                              const float* s, const float* stats, const float* out, int64_t ld_out,
+                              const float* grad_out, int64_t ld_grad,
+                              float* grad_x, int64_t ld_grad_x, float* grad_s, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Dense node transform (the layers' keras Dense / ops.matmul), one launch:
  *   out[i,:] (+)= ACT( bias + x0[i,:K0] @ W0 + x1[i,:K1] @ W1 )
  * Replaces GINConv's MLP Dense (gin_conv.py:129-162, applied at :225),

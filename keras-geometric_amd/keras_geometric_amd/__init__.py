@@ -9,6 +9,7 @@ from . import _native, graph, ops
 from .graph import CSRGraph, build_csr, clear_cache
 from .layers import (
     AggregatorFactory,
+    AttentionPooling,
     BatchGlobalPooling,
     GATv2Conv,
     GCNConv,
@@ -16,6 +17,7 @@ from .layers import (
     GlobalPooling,
     MessagePassing,
     SAGEConv,
+    Set2Set,
     set_random_seed,
 )
 from .utils import GraphData, add_self_loops, batch_graphs, compute_gcn_normalization
@@ -24,6 +26,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "AggregatorFactory",
+    "AttentionPooling",
     "BatchGlobalPooling",
     "CSRGraph",
     "GATv2Conv",
@@ -33,6 +36,7 @@ __all__ = [
     "GraphData",
     "MessagePassing",
     "SAGEConv",
+    "Set2Set",
     "add_self_loops",
     "batch_graphs",
     "build_csr",

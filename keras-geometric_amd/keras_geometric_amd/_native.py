@@ -25,6 +25,8 @@ FUSED_PRE_GIN, FUSED_ACCUMULATE, FUSED_SHARE_GPU, FUSED_RELU, FUSED_CU_SPLIT = 1
 CSR_SELF_LOOPS, CSR_SEGMENT_ONLY, CSR_GCN_NORM = 1, 2, 4
 DENSE_RELU, DENSE_ACCUMULATE = 1, 2
 DENSE_MAX_K, DENSE_MAX_N = 256, 256
+POOL_SCORE_TANH = 1
+POOL_MAX_F = 256
 
 REDUCE_IDS = {"sum": SUM, "mean": MEAN, "max": MAX, "min": MIN, "std": STD}
 
@@ -125,6 +127,14 @@ _SIGNATURES = {
         _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
         _i32p, _f32p, _f32p, _i64, _f32p, _int, _int, ctypes.c_float,
         _f32p, _i64, _f32p, _f32p, _f32p, _i32p, ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p,
+    ],
+    "kgx_softmax_pool": [
+        _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64, _i32p, _f32p, _i64, _i64,
+        _f32p, _f32p, _f32p, _int, _f32p, _f32p, _i64, _f32p, _f32p, ctypes.c_void_p,
+    ],
+    "kgx_softmax_pool_backward": [
+        _i64, _i64, _i32p, _f32p, _i64, _i64, _f32p, _f32p, _f32p, _i64, _f32p, _i64, _f32p, _i64, _f32p,
+        ctypes.c_void_p,
     ],
     "kgx_dense": [
         _i64, _f32p, _i64, _i64, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, _f32p, _i64, ctypes.c_void_p,

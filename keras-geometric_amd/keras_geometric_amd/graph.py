@@ -193,7 +193,9 @@ def build_csr(
     return g
 
 
-def _build_schedule(g: CSRGraph, split_len: int) -> None:
+def _build_schedule(g: CSRGraph, split_len: int, tails: bool = True) -> None:
+    """tails=False: the item list alone, without the short-row suffix and the
+    tiny-row records the aggregation kernels take (a pooling schedule)."""
     dev = g.device
     n = g.n_dst
     if split_len > 0:
@@ -225,8 +227,72 @@ def _build_schedule(g: CSRGraph, split_len: int) -> None:
         raise RuntimeError("kgx schedule: split list overflow")
     g.items = items[: g.n_items]
     g.split = split[: max(g.n_split, 0)]
+    if not tails:
+        return
     g.n_long = short_suffix_start(g.items)
     _refresh_tiny(g)
+
+
+# ---------------------------------------------------------------------------
+# Pooling schedules (kgx_softmax_pool)
+# ---------------------------------------------------------------------------
+# Largest chunk of a pooled segment.  default_split_len sizes chunks for edge
+# lists and stops at 8192, about 1200 items on a 10M-node graph; a readout's
+# segment is rows of x read once, and it wants enough chunks to fill the
+# resident lane groups.  Chosen by tools/bench_softmax_pool.py (DESIGN.md,
+# "Attention readouts"); KGX_POOL_CHUNK overrides it.
+POOL_CHUNK_MAX = 1024
+_POOL_TARGET_ITEMS = 2048
+
+
+def pool_chunk_len(n_nodes: int) -> int:
+    """Chunk length for pooling segments of up to n_nodes rows: a power of two
+    in [64, POOL_CHUNK_MAX] that cuts the largest segment into about
+    _POOL_TARGET_ITEMS chunks (a 5000-node graph is 79 chunks of 64, not one
+    lane group's 5000-row walk)."""
+    env = os.environ.get("KGX_POOL_CHUNK")
+    if env:
+        return _pow2_floor(int(env))
+    return int(min(POOL_CHUNK_MAX, max(64, _pow2_floor(max(n_nodes // _POOL_TARGET_ITEMS, 1)))))
+
+
+_SINGLE_SEGMENTS: "OrderedDict[tuple, CSRGraph]" = OrderedDict()
+
+
+def single_segment_graph(n_nodes: int, device: torch.device, chunk_len: int | None = None) -> CSRGraph:
+    """The one-row segment CSR of a single graph (rowptr = [0, N], identity
+    slot -> node map: `col` is None), built without a sort and scheduled by
+    kgx_schedule_build with the pooling chunk length (cached per size)."""
+    chunk = pool_chunk_len(n_nodes) if chunk_len is None else int(chunk_len)
+    key = (int(n_nodes), str(torch.device(device)), chunk)
+    g = _SINGLE_SEGMENTS.get(key)
+    if g is None:
+        dev = torch.device(device)
+        g = CSRGraph(
+            n_src=n_nodes, n_dst=1, n_input_edges=n_nodes, kept=n_nodes, max_degree=n_nodes, flags=nat.CSR_SEGMENT_ONLY,
+            rowptr=torch.tensor([0, n_nodes], dtype=torch.int32, device=dev), col=None, eid=None,
+            deg=torch.tensor([n_nodes], dtype=torch.int32, device=dev),
+        )
+        _build_schedule(g, chunk, tails=False)
+        _SINGLE_SEGMENTS[key] = g
+        while len(_SINGLE_SEGMENTS) > 16:
+            _SINGLE_SEGMENTS.popitem(last=False)
+    return g
+
+
+def segment_of_node(g: CSRGraph) -> torch.Tensor | None:
+    """int32 [n_src]: the segment (row) every node pools into, -1 for nodes in
+    none (dropped ids); None for a single_segment_graph (all in segment 0).
+    Cached on the graph: kgx_softmax_pool_backward's `seg`."""
+    if g.col is None:
+        return None
+    seg = g.extras.get("segment_of_node")
+    if seg is None:
+        seg = torch.full((g.n_src,), -1, dtype=torch.int32, device=g.device)
+        if g.kept:
+            seg[g.col.long()] = row_of_slot(g)
+        g.extras["segment_of_node"] = seg
+    return seg
 
 
 def _refresh_tiny(g: CSRGraph) -> None:

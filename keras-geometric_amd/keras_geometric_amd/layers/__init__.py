@@ -10,6 +10,7 @@ from .aggregators import (
     StdAggregator,
     SumAggregator,
 )
+from .attention_pooling import AttentionPooling, Set2Set
 from .base import Dense, Layer, Sequential, set_random_seed
 from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
@@ -21,6 +22,7 @@ from .sage_conv import SAGEConv
 __all__ = [
     "Aggregator",
     "AggregatorFactory",
+    "AttentionPooling",
     "BatchGlobalPooling",
     "Dense",
     "GATv2Conv",
@@ -35,6 +37,7 @@ __all__ = [
     "PoolingAggregator",
     "SAGEConv",
     "Sequential",
+    "Set2Set",
     "StdAggregator",
     "SumAggregator",
     "set_random_seed",

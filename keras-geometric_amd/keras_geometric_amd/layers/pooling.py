@@ -11,9 +11,10 @@ tensor) and the pooling is one kgx_spmm launch:
   the MEAN reduce's: for an integer count the two guards agree);
   max  -> segment_max WITHOUT the aggregators' isinf guard (KGX_EPI_RAW):
   an empty graph pools to -inf, as keras.ops.segment_max does.
-Differentiable through ops.aggregate's autograd.  AttentionPooling / Set2Set
-(attention_pooling.py) are dense per-graph MLP/LSTM readouts outside the
-propagate path and are not provided.
+Differentiable through ops.aggregate's autograd.  The attention readouts
+AttentionPooling / Set2Set (pooling/attention_pooling.py) live in
+layers/attention_pooling.py, on the fused softmax-pooling kernel
+(kgx_softmax_pool); their batched form reuses segment_graph below.
 """
 
 from __future__ import annotations

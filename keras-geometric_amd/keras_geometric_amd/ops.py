@@ -6,6 +6,7 @@ torch.compile / symbolic tracing sees shapes without running the GPU.
 
   kgx::spmm   fused gather -> message -> segment {sum,mean,max,min,std} -> epilogue
   kgx::gatv2  fused GATv2 attention aggregation
+  kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
   kgx::gather_rows, kgx::scatter_f32   row movement helpers
 """
 
@@ -1276,3 +1277,242 @@ def dense(
     if x1 is not None:
         y = torch.addmm(y, x1, W1)
     return torch.relu(y) if relu else y
+
+
+# ---------------------------------------------------------------------------
+# Attention readouts: fused segment softmax + weighted sum (kgx_softmax_pool)
+# ---------------------------------------------------------------------------
+def _softmax_pool_impl(x, rowptr, rows, items, split, idx, s, score_u, score_c, tanh, n_slots, save):
+    if x.dtype != torch.float32:
+        raise TypeError(f"kgx kernels compute in fp32; got {x.dtype}")
+    s, score_c = _f32c(s), _f32c(score_c)
+    score_u = None if score_u is None else _aligned16(score_u)  # a misaligned u would cost the float4 lanes
+    dev = nat.require_device(x, rowptr, rows, items, split, idx, s, score_u, score_c)
+    n_seg = rowptr.numel() - 1
+    N, F = x.shape
+    fused = score_u is not None
+    out = torch.empty((n_seg, F), dtype=torch.float32, device=dev)
+    stats = torch.empty((n_seg if save else 0, 2), dtype=torch.float32, device=dev)
+    # nodes in no segment keep score 0 (they pool nowhere and get zero gradient)
+    s_out = torch.zeros(N if fused else 0, dtype=torch.float32, device=dev)
+    if n_seg == 0:
+        return out, stats, s_out
+    n_items = 0 if items is None else items.shape[0]
+    n_split = 0 if split is None else split.shape[0]
+    partials = None
+    if items is not None and n_split > 0:
+        partials = torch.empty((n_slots, F + 2), dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_softmax_pool(
+            nat.ptr(rowptr), nat.ptr(rows), n_seg, nat.ptr(items), n_items, nat.ptr(split), n_split,
+            nat.ptr(idx), nat.ptr(x), x.stride(0) if N > 1 else max(x.stride(0), F), F,
+            nat.ptr(s), nat.ptr(score_u), nat.ptr(score_c), nat.POOL_SCORE_TANH if (fused and tanh) else 0,
+            nat.ptr(s_out) if fused else None, nat.ptr(out), out.stride(0),
+            nat.ptr(stats) if save else None, nat.ptr(partials), nat.stream(dev),
+        ),
+        "kgx_softmax_pool",
+    )
+    return out, stats, s_out
+
+
+@torch.library.custom_op("kgx::softmax_pool_save", mutates_args=())
+def softmax_pool_save(
+    x: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    idx: Optional[torch.Tensor],
+    s: Optional[torch.Tensor],
+    score_u: Optional[torch.Tensor],
+    score_c: Optional[torch.Tensor],
+    tanh: bool,
+    n_slots: int,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """kgx::softmax_pool that also returns the per-segment softmax statistics
+    [n_seg, 2] and, for fused scores, the scores [N] (empty for given ones)."""
+    return _softmax_pool_impl(x, rowptr, rows, items, split, idx, s, score_u, score_c, tanh, n_slots, True)
+
+
+@softmax_pool_save.register_fake
+def _softmax_pool_save_fake(x, rowptr, rows, items, split, idx, s, score_u, score_c, tanh, n_slots):
+    n = rowptr.shape[0] - 1
+    return (x.new_empty((n, x.shape[1])), x.new_empty((n, 2)),
+            x.new_empty((x.shape[0] if score_u is not None else 0,)))
+
+
+@torch.library.custom_op("kgx::softmax_pool", mutates_args=())
+def softmax_pool_op(
+    x: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    idx: Optional[torch.Tensor],
+    s: Optional[torch.Tensor],
+    score_u: Optional[torch.Tensor],
+    score_c: Optional[torch.Tensor],
+    tanh: bool,
+    n_slots: int,
+) -> torch.Tensor:
+    return _softmax_pool_impl(x, rowptr, rows, items, split, idx, s, score_u, score_c, tanh, n_slots, False)[0]
+
+
+@softmax_pool_op.register_fake
+def _softmax_pool_fake(x, rowptr, rows, items, split, idx, s, score_u, score_c, tanh, n_slots):
+    return x.new_empty((rowptr.shape[0] - 1, x.shape[1]))
+
+
+@torch.library.custom_op("kgx::softmax_pool_backward", mutates_args=())
+def softmax_pool_backward(
+    x: torch.Tensor,
+    seg: Optional[torch.Tensor],
+    s: torch.Tensor,
+    stats: torch.Tensor,
+    out: torch.Tensor,
+    grad_out: torch.Tensor,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """(grad_x [N, F], grad_s [N]) of kgx::softmax_pool, one pass over x."""
+    s, stats, out, grad_out = _f32c(s), _f32c(stats), _f32c(out), _f32c(grad_out)
+    dev = nat.require_device(x, seg, s, stats, out, grad_out)
+    N, F = x.shape
+    grad_x = torch.empty((N, F), dtype=torch.float32, device=dev)
+    grad_s = torch.empty(N, dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_softmax_pool_backward(
+            N, out.shape[0], nat.ptr(seg), nat.ptr(x), x.stride(0) if N > 1 else max(x.stride(0), F), F,
+            nat.ptr(s), nat.ptr(stats), nat.ptr(out), out.stride(0), nat.ptr(grad_out), grad_out.stride(0),
+            nat.ptr(grad_x), grad_x.stride(0), nat.ptr(grad_s), nat.stream(dev),
+        ),
+        "kgx_softmax_pool_backward",
+    )
+    return grad_x, grad_s
+
+
+@softmax_pool_backward.register_fake
+def _softmax_pool_backward_fake(x, seg, s, stats, out, grad_out):
+    return x.new_empty(x.shape), x.new_empty((x.shape[0],))
+
+
+def softmax_pool_supported(x: torch.Tensor) -> bool:
+    """Inputs kgx_softmax_pool takes: fp32 rows of 1..256 features with unit
+    column stride and a row stride that covers them (any row alignment: rows
+    that are not 16-byte aligned take the kernel's scalar lanes)."""
+    return (x.dim() == 2 and x.dtype == torch.float32 and 0 < x.shape[1] <= nat.POOL_MAX_F and x.stride(1) == 1
+            and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1]))
+
+
+def _pool_args(g: CSRGraph):
+    items, _, split, _, n_slots = g.work(False)
+    return g.rowptr, g.rows, items, split, g.col, n_slots
+
+
+def _segment_sum_1d(g: CSRGraph, v: torch.Tensor) -> torch.Tensor:
+    """[n_seg]: per-segment sum of a per-node vector, in a fixed order."""
+    if g.col is None:
+        return v.sum().reshape(1)
+    return aggregate(g, v.unsqueeze(1).contiguous(), "sum", exact=True).reshape(-1)
+
+
+class _SoftmaxPoolFn(torch.autograd.Function):
+    """Autograd of the fused softmax pooling.  The forward keeps out, the
+    per-segment (max, denominator) and the scores; kgx_softmax_pool_backward
+    gives (grad_x, grad_s) in one pass over x.  For fused scores s = act(x u +
+    c[g]) the chain is finished with torch ops: dz = grad_s * act'(s),
+    grad_x += dz (x) u, grad_u = x^T dz, grad_c = segment sum of dz."""
+
+    @staticmethod
+    def forward(ctx, x, s, score_u, score_c, g, tanh):
+        from . import graph as G
+
+        ctx.g, ctx.tanh, ctx.fused = g, bool(tanh), score_u is not None
+        a = _pool_args(g)
+        out, stats, s_out = _timed(lambda: torch.ops.kgx.softmax_pool_save(
+            x, *a[:5], s, score_u, score_c, bool(tanh), a[5]))
+        ctx.seg = G.segment_of_node(g)
+        ctx.save_for_backward(x, s_out if ctx.fused else s, score_u, stats, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, s, score_u, stats, out = ctx.saved_tensors
+        grad_x, grad_s = torch.ops.kgx.softmax_pool_backward(x, ctx.seg, s, stats, out, grad_out.contiguous())
+        if not ctx.fused:
+            return grad_x, grad_s, None, None, None, None
+        dz = grad_s * (1.0 - s * s) if ctx.tanh else grad_s
+        grad_u = grad_c = None
+        if ctx.needs_input_grad[0]:
+            grad_x.addcmul_(dz.unsqueeze(1), score_u.unsqueeze(0))
+        if ctx.needs_input_grad[2]:
+            grad_u = (x * dz.unsqueeze(1)).sum(0)  # a fixed-order column sum (bit-reproducible)
+        if ctx.needs_input_grad[3]:
+            grad_c = _segment_sum_1d(ctx.g, dz)
+        return grad_x, None, grad_u, grad_c, None, None
+
+
+def _softmax_pool_composed(g: CSRGraph, x, s, score_u, score_c, tanh):
+    """The same pooling from torch ops (differentiable by torch autograd), for
+    inputs kgx_softmax_pool rejects: F > 256 or a strided last dimension."""
+    from . import graph as G
+
+    seg = G.segment_of_node(g)
+    n_seg = g.n_dst
+    if seg is None:
+        if s is None:
+            z = x @ score_u + score_c[0]
+            s = torch.tanh(z) if tanh else z
+        w = torch.softmax(s, dim=0)
+        return (w.unsqueeze(1) * x).sum(0, keepdim=True)
+    keep = (seg >= 0).nonzero().reshape(-1)
+    sg = seg[keep].long()
+    xk = x[keep]
+    if s is None:
+        z = xk @ score_u + score_c[sg]
+        sk = torch.tanh(z) if tanh else z
+    else:
+        sk = s[keep]
+    m = torch.full((n_seg,), float("-inf"), dtype=x.dtype, device=x.device)
+    m = m.scatter_reduce(0, sg, sk.detach(), "amax", include_self=True)
+    e = torch.exp(sk - m[sg])
+    den = torch.zeros(n_seg, dtype=x.dtype, device=x.device).index_add(0, sg, e)
+    w = e / den[sg]
+    return torch.zeros((n_seg, x.shape[1]), dtype=x.dtype, device=x.device).index_add(0, sg, w.unsqueeze(1) * xk)
+
+
+def softmax_pool(
+    g: CSRGraph,
+    x: torch.Tensor,
+    s: torch.Tensor | None = None,
+    *,
+    score_u: torch.Tensor | None = None,
+    score_c: torch.Tensor | None = None,
+    tanh: bool = False,
+) -> torch.Tensor:
+    """out[r, :] = sum_{i in segment r} softmax_r(s)_i * x[i, :] -> [g.n_dst, F].
+
+    g: a segment CSR (layers.pooling.segment_graph / build_csr(segment_only=True)
+    over a batch vector, col = node per slot) or graph.single_segment_graph.
+    Scores are either given (`s` [N]) or fused: s_i = act(x_i . score_u +
+    score_c[r]) with act = tanh when `tanh` (Set2Set's attention Dense),
+    computed in the pooling kernel from the row it has loaded.  Differentiable
+    in x, s, score_u, score_c.  F > 256 or a strided last dimension run as the
+    composed torch form on the same device."""
+    if (s is None) == (score_u is None):
+        raise ValueError("softmax_pool: exactly one of s and score_u")
+    if score_u is not None and score_c is None:
+        raise ValueError("softmax_pool: score_u needs score_c")
+    if tanh and score_u is None:
+        raise ValueError("softmax_pool: tanh applies to fused scores (score_u) only")
+    if x.dim() != 2 or x.shape[0] != g.n_src:
+        raise ValueError(f"softmax_pool: x must be [{g.n_src}, F], got {tuple(x.shape)}")
+    nat.require_device(x, s, score_u, score_c)
+    if not softmax_pool_supported(x):
+        return _softmax_pool_composed(g, x, s, score_u, score_c, tanh)
+    if s is not None:
+        s = s.reshape(-1)
+    if score_u is not None:
+        score_u, score_c = score_u.reshape(-1), score_c.reshape(-1)
+    if _needs_grad(x, s, score_u, score_c):
+        return _SoftmaxPoolFn.apply(x, s, score_u, score_c, g, bool(tanh))
+    a = _pool_args(g)
+    return _timed(lambda: torch.ops.kgx.softmax_pool(x, *a[:5], s, score_u, score_c, bool(tanh), a[5]))
