@@ -437,7 +437,8 @@ int kgx_spmm_max_backward(int reduce, int raw, const int32_t* rowptr, int64_t n_
  *   _softmax_by_target, alpha*h_j, _aggregate_messages and the concat-mode
  *   _final_update (gatv2_conv.py:241-266, 268-311, 313-335, 337-352).
  * h_src/h_dst: [n, heads*channels] row-major with leading dimension ld_h.
- * partials: n_slots * (heads*channels + 2*heads) floats when items are split.
+ * partials: n_slots * ld_p floats when items are split, ld_p = heads*channels +
+ *   2*heads rounded up to a multiple of 4 (each slot starts 16-byte aligned).
  * stats (optional, [n, 2*heads]): per row and head the softmax max and
  * denominator (sum + 1e-10), kept for kgx_gatv2_backward.
  * drop_key (optional): attention dropout (training, gatv2_conv.py:252-253):

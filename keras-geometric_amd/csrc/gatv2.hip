@@ -43,7 +43,8 @@ struct GatArgs {
   float* out;
   int64_t ld_o;
   const float* bias;
-  float* partials;  // per slot: [H*C acc | H m | H l]
+  float* partials;  // per slot: [H*C acc | H m | H l], slots ld_p floats apart
+  int64_t ld_p;     // H*C + 2H rounded up to a multiple of 4: every slot starts 16-byte aligned (odd H)
   float* stats;     // optional [n, 2H]: per row and head, the softmax max m and denominator l + 1e-10
   // attention dropout (training): alpha_e *= keep(seed, drop_key[e], head) / (1 - p)
   const int32_t* drop_key;
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_kernel(GatArgs a) {
 
     if (!valid) continue;
     if (slot >= 0) {
-      float* p = a.partials + int64_t(slot) * (HC + 2 * a.H);
+      float* p = a.partials + int64_t(slot) * a.ld_p;
       float accf[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) accf[k] = float(acc[k]);
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_fixup_kernel(GatArgs a) {
     // (clamped, unconditional), the running max rescaled online as in the main
     // kernel: a hub row's ~160 partials cost ~10 load latencies, not ~320.
     constexpr int B = 16;
-    const int64_t ld_p = HC + 2 * a.H;
+    const int64_t ld_p = a.ld_p;
     float M = -__builtin_inff();
     double L = 0.0, acc[K];
 #pragma unroll
@@ -366,6 +367,7 @@ extern "C" int kgx_gatv2(const int32_t* rowptr, const int32_t* rows, int64_t n_r
   a.ld_o = ld_out;
   a.bias = bias;
   a.partials = partials;
+  a.ld_p = (HC + 2 * heads + 3) / 4 * 4;
   a.stats = stats;
   KGX_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, KGX_ERR_ARG, "kgx_gatv2: dropout p must be in [0, 1)");
   if (drop_key && drop_p > 0.0f) {

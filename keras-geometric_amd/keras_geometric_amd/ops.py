@@ -586,7 +586,8 @@ def _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, chann
     n_split = 0 if split is None else split.shape[0]
     partials = None
     if items is not None and n_split > 0:
-        partials = torch.empty((n_slots, HC + 2 * heads), dtype=torch.float32, device=dev)
+        # per slot [HC acc | heads m | heads l], padded to whole float4s (kgx.h)
+        partials = torch.empty((n_slots, (HC + 2 * heads + 3) // 4 * 4), dtype=torch.float32, device=dev)
     nat.check(
         nat.lib().kgx_gatv2(
             nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split,
