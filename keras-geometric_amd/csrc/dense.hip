@@ -30,24 +30,12 @@
 
 #include "kgx_bf16x3.h"
 #include "kgx_internal.h"
+#include "kgx_mfma.h"
 
 namespace kgx {
 namespace {
 
 constexpr int kBM = 32;  // rows per tile
-
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS ops
-// (lgkmcnt), not its outstanding global loads / stores (vmcnt).
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct DenseArgs {
   int64_t M;
@@ -182,30 +170,30 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
       int64_t rows = a.M - r0;
       rows = rows < 0 ? 0 : (rows > kBM ? kBM : rows);
       const uint64_t addr = reinterpret_cast<uint64_t>(base) + uint64_t(r0 * ld * 4);
-      u32x4 d;
+      u32x4_t d;
       d[0] = __builtin_amdgcn_readfirstlane(uint32_t(addr));
       d[1] = __builtin_amdgcn_readfirstlane(uint32_t(addr >> 32) & 0xffffu);
       d[2] = __builtin_amdgcn_readfirstlane(uint32_t(rows * ld * 4));
       d[3] = 0x00020000u;
       return d;
     };
-    auto ld16 = [](f32x4& v, uint32_t off, const u32x4& d) {
+    auto ld16 = [](f32x4_t& v, uint32_t off, const u32x4_t& d) {
       asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v) : "v"(off), "s"(d) : "memory");
     };
-    f32x4 P[NSETS][NL], Q[NSETS][NL];  // register sets (Q: x1 columns)
-    auto load_tile = [&](f32x4(&p)[NL], f32x4(&q)[NL], int64_t tile) {
-      const u32x4 d0 = rsrc(a.x0 ? a.x0 : a.x1, a.ld0, tile);
+    f32x4_t P[NSETS][NL], Q[NSETS][NL];  // register sets (Q: x1 columns)
+    auto load_tile = [&](f32x4_t(&p)[NL], f32x4_t(&q)[NL], int64_t tile) {
+      const u32x4_t d0 = rsrc(a.x0 ? a.x0 : a.x1, a.ld0, tile);
 #pragma unroll
       for (int j = 0; j < NL; ++j) ld16(p[j], vo0[j], d0);
       if constexpr (TWO) {
-        const u32x4 d1 = rsrc(a.x1, a.ld1, tile);
+        const u32x4_t d1 = rsrc(a.x1, a.ld1, tile);
 #pragma unroll
         for (int j = 0; j < NL; ++j) ld16(q[j], vo1[j], d1);
       }
     };
     // wait until at most `newer` loads are outstanding, then pin the set's
     // registers behind the wait (the empty asm "redefines" them)
-    auto wait_set = [&](f32x4(&p)[NL], f32x4(&q)[NL], auto newer) {
+    auto wait_set = [&](f32x4_t(&p)[NL], f32x4_t(&q)[NL], auto newer) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(newer)::value) : "memory");
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
         if constexpr (TWO) asm volatile("" : "+v"(q[j]));
       }
     };
-    auto stage = [&](const f32x4(&p)[NL], const f32x4(&q)[NL], int buf) {
+    auto stage = [&](const f32x4_t(&p)[NL], const f32x4_t(&q)[NL], int buf) {
       // fast path: paired conversions (split3_pair_rn, ~4.5 VALU per element:
       // the producer's split must fit in the issue slots the consumers' MFMAs
       // leave free on its SIMD).  chk = sum of 2|x| over the thread's slots
@@ -225,9 +213,9 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
         const int row = srow0 + j * RSTEP;
-        f32x4 x = p[j];
+        f32x4_t x = p[j];
         if constexpr (TWO)
-          x = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, p[j]) | __builtin_bit_cast(u32x4, q[j]));
+          x = __builtin_bit_cast(f32x4_t, __builtin_bit_cast(u32x4_t, p[j]) | __builtin_bit_cast(u32x4_t, q[j]));
         chk0 = fmaf(fabsf(x[0]), 2.0f, chk0);
         chk1 = fmaf(fabsf(x[1]), 2.0f, chk1);
         chk0 = fmaf(fabsf(x[2]), 2.0f, chk0);
@@ -243,9 +231,9 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
         const int row = srow0 + j * RSTEP;
-        f32x4 x = p[j];
+        f32x4_t x = p[j];
         if constexpr (TWO)  // each slot read zero bits from one of the two descriptors
-          x = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, p[j]) | __builtin_bit_cast(u32x4, q[j]));
+          x = __builtin_bit_cast(f32x4_t, __builtin_bit_cast(u32x4_t, p[j]) | __builtin_bit_cast(u32x4_t, q[j]));
         bf16x4_t ph, pm, pl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -303,14 +291,14 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
 #pragma unroll
       for (int m = 0; m < NST; ++m) {
         const int row = prow0 + m * PRSTEP;
-        f32x4 v = *reinterpret_cast<const f32x4*>(&Os[ob][row][4 * pc4]);
+        f32x4_t v = *reinterpret_cast<const f32x4_t*>(&Os[ob][row][4 * pc4]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           v[j] = v[j] + ob4[j];
           if (a.relu) v[j] = fmaxf(v[j], 0.0f);
         }
         const uint32_t off = ocol < a.N ? uint32_t((row * a.ld_out + ocol) * 4) : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, off, 0, 0);
       }
     };
     using Zero = std::integral_constant<int, 0>;
@@ -414,17 +402,17 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
                                              0x00020000);
   };
   auto lprev_rs = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0, 0x00020000);  // zero records: first tile's stores dropped
-  f32x4 lov[2], lb4;
+  f32x4_t lov[2], lb4;
   auto lstore_prev = [&]() {
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      f32x4 v = lov[m];
+      f32x4_t v = lov[m];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         v[j] = v[j] + lb4[j];
         if (a.relu) v[j] = fmaxf(v[j], 0.0f);
       }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), lprev_rs, lo_off,
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), lprev_rs, lo_off,
                                              int(m * LROWS * a.ld_out * 4), 0);
     }
   };
@@ -432,9 +420,9 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
   int64_t t = pid;
   for (int64_t i = 0; i < my_tiles; ++i, t += n_pairs) {
     const int buf = int(i & 1);
-    f32x4 acc[2];
-    acc[0] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    acc[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t acc[2];
+    acc[0] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+    acc[1] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
     // A fragments are software-pipelined one k-step ahead: the six LDS reads
     // of step s + 1 are issued (inline asm, so the scheduler cannot sink them
     // next to their use) before step s's 12 MFMAs, and step s waits with
@@ -457,7 +445,7 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.l[r]) : "v"(lane), "i"(2 * P + R * r + K));
       }
     };
-    auto wait_frags = [](Frags& f, f32x4(&acc)[2], auto N) {
+    auto wait_frags = [](Frags& f, f32x4_t(&acc)[2], auto N) {
       asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(decltype(N)::value) : "memory");
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
@@ -553,8 +541,8 @@ __global__ __launch_bounds__(64 * (WAVES + kProducerWaves)) void dense_kernel(De
   if constexpr (LS) {  // the last tile's rows (written before the last barrier)
     const int lb = int((my_tiles - 1) & 1);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) lov[m] = *reinterpret_cast<const f32x4*>(&Os[lb][lrow0 + m * LROWS][4 * lc4]);
-    lb4 = *reinterpret_cast<const f32x4*>(&Ob[4 * lc4]);
+    for (int m = 0; m < 2; ++m) lov[m] = *reinterpret_cast<const f32x4_t*>(&Os[lb][lrow0 + m * LROWS][4 * lc4]);
+    lb4 = *reinterpret_cast<const f32x4_t*>(&Ob[4 * lc4]);
     lstore_prev();
   }
 }
@@ -569,23 +557,13 @@ int launch(const DenseArgs& a, hipStream_t s) {
     if (!a.accumulate && a.vec_out && !a.pstore && a.debug == 0)
       k = a.K1 > 0 ? dense_kernel<KS, WAVES, false, true, true> : dense_kernel<KS, WAVES, false, false, true>;
   }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64 * (WAVES + kProducerWaves), 0) != hipSuccess ||
-      per_cu <= 0)
-    per_cu = 1;
+  constexpr int threads = 64 * (WAVES + kProducerWaves);
   const int64_t n_tiles = (a.M + kBM - 1) / kBM;
-  const int64_t cap = int64_t(per_cu) * cus;
+  const int64_t cap = occupancy_blocks(k, threads, 1);
   const int64_t want = n_tiles * a.cg_count;
   int64_t grid = want < cap ? want : cap;
   if (a.cg_count == 2) grid = grid >= 16 ? grid / 16 * 16 : grid / 2 * 2;  // whole XCD pairs
-  hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * (WAVES + kProducerWaves)), 0, s, a);
+  hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(threads), 0, s, a);
   KGX_CHECK_LAUNCH();
   return KGX_OK;
 }

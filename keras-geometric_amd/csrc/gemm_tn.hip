@@ -37,13 +37,10 @@
 
 #include "kgx_bf16x3.h"
 #include "kgx_internal.h"
+#include "kgx_mfma.h"
 
 namespace kgx {
 namespace {
-
-typedef short kgx_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float kgx_f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t kgx_u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 128;          // dW tile edge per block
 constexpr int kTn = 256;            // threads per block (4 waves)
@@ -61,12 +58,12 @@ struct TnArgs {
 };
 
 struct Planes {
-  kgx_bf16x8_t hi, mid, lo;
+  bf16x8_t hi, mid, lo;
 };
 
 // eight f32 values -> three bf16x8 planes (pairs through split3_pair_rn)
 __device__ __forceinline__ Planes split8(const float (&v)[8]) {
-  kgx_u32x4_t h, m, l;
+  u32x4_t h, m, l;
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     uint32_t a, b, c;
@@ -76,13 +73,13 @@ __device__ __forceinline__ Planes split8(const float (&v)[8]) {
     l[p] = c;
   }
   Planes r;
-  r.hi = __builtin_bit_cast(kgx_bf16x8_t, h);
-  r.mid = __builtin_bit_cast(kgx_bf16x8_t, m);
-  r.lo = __builtin_bit_cast(kgx_bf16x8_t, l);
+  r.hi = __builtin_bit_cast(bf16x8_t, h);
+  r.mid = __builtin_bit_cast(bf16x8_t, m);
+  r.lo = __builtin_bit_cast(bf16x8_t, l);
   return r;
 }
 
-__device__ __forceinline__ kgx_f32x4_t mfma6(const Planes& a, const Planes& b, kgx_f32x4_t acc) {
+__device__ __forceinline__ f32x4_t mfma6(const Planes& a, const Planes& b, f32x4_t acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.mid, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.mid, b.hi, acc, 0, 0, 0);
@@ -103,10 +100,9 @@ __device__ __forceinline__ kgx_f32x4_t mfma6(const Planes& a, const Planes& b, k
 // Element e of lane c's float4 is column 4 c + e: MFMA e of a k (or m) block
 // takes element e of every lane, so its 16 output rows are the columns
 // k0 + 4 c + e, c = 0..15 (a strided set; the store unscrambles it).
-typedef float kgx_f32x4v_t __attribute__((ext_vector_type(4)));
 
 struct StepVals {
-  kgx_f32x4v_t p[8], d[8];
+  f32x4_t p[8], d[8];
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t step_rsrc(const float* base, int64_t ld, int64_t s, int64_t N) {
@@ -125,8 +121,8 @@ __device__ __forceinline__ void load_step(StepVals& v, const TnArgs& a, int64_t 
   const auto rd = step_rsrc(a.D, a.ldd, s, a.N);
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
-    v.p[t] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po, int(t * a.ldp * 4), 0));
-    v.d[t] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof, int(t * a.ldd * 4), 0));
+    v.p[t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po, int(t * a.ldp * 4), 0));
+    v.d[t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof, int(t * a.ldd * 4), 0));
   }
 }
 
@@ -147,11 +143,11 @@ __global__ __launch_bounds__(kTn, 1) void gemm_tn_kernel(TnArgs a) {
   const uint32_t dof = mq < a.M ? uint32_t((8 * g * a.ldd + mq) * 4) : 0x80000000u;
   const bool wave_live = k0 < a.K && m0 < a.M;
 
-  kgx_f32x4_t acc[4][4];
+  f32x4_t acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = kgx_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float dbs[4] = {0.f, 0.f, 0.f, 0.f};
   int bad = 0;
 
@@ -268,15 +264,14 @@ constexpr int kPlaneBytes = kStep * kTile * 2;  // one [32][128] bf16 plane: 8 K
 constexpr int kBufBytes = 6 * kPlaneBytes;      // P hi/mid/lo, D hi/mid/lo
 constexpr int kSets = 4;                        // register sets: one consumed, three in flight
 
-typedef short kgx_bf16x4_t __attribute__((ext_vector_type(4)));
-typedef kgx_bf16x4_t __attribute__((address_space(3))) lds_bf16x4_t;
+typedef bf16x4_t __attribute__((address_space(3))) lds_bf16x4_t;
 
 // byte offset of 16-byte chunk ch (0..15) of plane row r: conflict-free for the
 // transposed reads of two 4-row blocks 8 rows apart (cdna_hip_programming.md T10, image (b))
 __device__ __forceinline__ int swz(int r, int ch) { return 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))); }
 
 struct LoadSet {
-  kgx_f32x4v_t p[2], d[2];
+  f32x4_t p[2], d[2];
 };
 
 // step s's loads; steps at or past s_end (the block's range) read 0 (a zero record count)
@@ -287,8 +282,8 @@ __device__ __forceinline__ void load_set(LoadSet& v, const TnArgs& a, int64_t s,
   const auto rd = step_rsrc(a.D, a.ldd, s, n_end);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    v.p[j] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po[j], 0, 0));
-    v.d[j] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof[j], 0, 0));
+    v.p[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po[j], 0, 0));
+    v.d[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof[j], 0, 0));
   }
 }
 
@@ -329,11 +324,11 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_lds_kernel(TnArgs a) {
     for (int j = 0; j < 4; ++j) offB[j][h] = rd_off(mw0 + 16 * j, h);
   }
 
-  kgx_f32x4_t acc[2][4];
+  f32x4_t acc[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = kgx_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float dbs[4] = {0.f, 0.f, 0.f, 0.f};
 
   // one step's values -> the split planes of LDS buffer b.  No per-value check: a value the split
@@ -347,7 +342,7 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_lds_kernel(TnArgs a) {
       const int off = swz(nrow[j], c4 >> 1) + 8 * (c4 & 1);
 #pragma unroll
       for (int o = 0; o < 2; ++o) {  // P, then D
-        const kgx_f32x4v_t x = o ? v.d[j] : v.p[j];
+        const f32x4_t x = o ? v.d[j] : v.p[j];
         uint32_t h0, m0, l0, h1, m1, l1;
         split3_pair_rn(x[0], x[1], h0, m0, l0);
         split3_pair_rn(x[2], x[3], h1, m1, l1);
@@ -371,8 +366,8 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_lds_kernel(TnArgs a) {
           (lds_bf16x4_t*)(const_cast<char*>(base) + plane * kPlaneBytes + off));
     };
     auto operand = [&](int plane, const int (&off)[2]) {
-      const kgx_bf16x4_t lo = rd(plane, off[0]), hi = rd(plane, off[1]);
-      return kgx_bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      const bf16x4_t lo = rd(plane, off[0]), hi = rd(plane, off[1]);
+      return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     };
     Planes B[4];
 #pragma unroll
@@ -487,7 +482,7 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_lds_kernel(TnArgs a) {
 constexpr int kPj = 4;  // float4 loads of P (and of D) per producer thread per step
 
 struct ProdSet {
-  kgx_f32x4v_t p[kPj], d[kPj];
+  f32x4_t p[kPj], d[kPj];
 };
 
 __device__ __forceinline__ void prod_load(ProdSet& v, const TnArgs& a, int64_t s, int64_t s_end,
@@ -497,8 +492,8 @@ __device__ __forceinline__ void prod_load(ProdSet& v, const TnArgs& a, int64_t s
   const auto rd = step_rsrc(a.D, a.ldd, s, n_end);
 #pragma unroll
   for (int j = 0; j < kPj; ++j) {
-    v.p[j] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po[j], 0, 0));
-    v.d[j] = __builtin_bit_cast(kgx_f32x4v_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof[j], 0, 0));
+    v.p[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rp, po[j], 0, 0));
+    v.d[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rd, dof[j], 0, 0));
   }
 }
 
@@ -522,11 +517,11 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_ws_kernel(TnArgs a) {
     asm volatile("" ::: "memory");
   };
 
-  kgx_f32x4_t acc[4][4];
+  f32x4_t acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = kgx_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float dbs[4] = {0.f, 0.f, 0.f, 0.f};
   // producer thread p: float4 q = p + 256 j of the step's [32][32] float4 grid -> node q >> 5, columns 4 (q & 31) ..
   const int p = t & 255;
@@ -550,7 +545,7 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_ws_kernel(TnArgs a) {
         const int off = swz(nrow[j], c4 >> 1) + 8 * (c4 & 1);
 #pragma unroll
         for (int o = 0; o < 2; ++o) {  // P, then D
-          const kgx_f32x4v_t x = o ? v.d[j] : v.p[j];
+          const f32x4_t x = o ? v.d[j] : v.p[j];
           uint32_t h0, m0, l0, h1, m1, l1;
           split3_pair_rn(x[0], x[1], h0, m0, l0);
           split3_pair_rn(x[2], x[3], h1, m1, l1);
@@ -601,8 +596,8 @@ __global__ __launch_bounds__(kTnL, 1) void gemm_tn_ws_kernel(TnArgs a) {
             (lds_bf16x4_t*)(const_cast<char*>(base) + plane * kPlaneBytes + off));
       };
       auto operand = [&](int plane, const int (&off)[2]) {
-        const kgx_bf16x4_t lo = rd(plane, off[0]), hi = rd(plane, off[1]);
-        return kgx_bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const bf16x4_t lo = rd(plane, off[0]), hi = rd(plane, off[1]);
+        return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       };
       Planes B[4];
 #pragma unroll

@@ -816,17 +816,13 @@ extern "C" int kgx_cu_split_census(int per32, int64_t n_blocks, int32_t* head_id
   hipStream_t s = as_stream(stream_);
   CuSplit* cs = cu_split(per32, s);
   KGX_REQUIRE(cs != nullptr, KGX_ERR_UNSUPPORTED, "kgx_cu_split_census: no CU split on this device / stream");
-  KGX_CHECK_HIP(hipEventRecord(cs->fork, s));
-  KGX_CHECK_HIP(hipStreamWaitEvent(cs->head, cs->fork, 0));
-  KGX_CHECK_HIP(hipStreamWaitEvent(cs->tail, cs->fork, 0));
+  SplitJoin sj;
+  KGX_CHECK_HIP(sj.fork(cs, s));
   hipLaunchKernelGGL(cu_census_kernel, dim3(unsigned(n_blocks)), dim3(64), 0, cs->head, head_ids, n_blocks);
   KGX_CHECK_LAUNCH();
   hipLaunchKernelGGL(cu_census_kernel, dim3(unsigned(n_blocks)), dim3(64), 0, cs->tail, tail_ids, n_blocks);
   KGX_CHECK_LAUNCH();
-  KGX_CHECK_HIP(hipEventRecord(cs->jh, cs->head));
-  KGX_CHECK_HIP(hipEventRecord(cs->jt, cs->tail));
-  KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jh, 0));
-  KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jt, 0));
+  KGX_CHECK_HIP(sj.join());
   KGX_CHECK_HIP(hipStreamSynchronize(s));
   n_cus[0] = cs->n_head;
   n_cus[1] = cs->n_tail;

@@ -55,8 +55,6 @@ inline unsigned grid_for(int64_t work_threads, int64_t cap_blocks = 2048) {
   return static_cast<unsigned>(b);
 }
 
-// Grid for a persistent grid-stride launch: as many blocks as are resident at
-// once (occupancy x CUs), never more than the work needs.
 inline int cu_count() {
   static int cus = 0;
   if (cus == 0) {
@@ -68,13 +66,22 @@ inline int cu_count() {
   return cus;
 }
 
+// Blocks of `kernel` (of `threads` threads) resident at once on `cus` CUs (0:
+// the whole device): the occupancy query's blocks per CU, or fallback_per_cu
+// where the query fails.
+template <typename Kern>
+int64_t occupancy_blocks(Kern kernel, int threads, int fallback_per_cu, int cus = 0) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0)
+    per_cu = fallback_per_cu;
+  return int64_t(per_cu) * (cus > 0 ? cus : cu_count());
+}
+
+// Grid for a persistent grid-stride launch: as many blocks as are resident at
+// once (occupancy x CUs), never more than the work needs.
 template <typename Kern>
 unsigned resident_grid(Kern kernel, int64_t groups_needed, int G) {
-  const int cus = cu_count();
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu <= 0)
-    per_cu = 4;
-  const int64_t cap = int64_t(per_cu) * cus;
+  const int64_t cap = occupancy_blocks(kernel, kBlock, 4);
   const int64_t need = (groups_needed * G + kBlock - 1) / kBlock;
   const int64_t g = need < cap ? need : cap;
   return unsigned(g < 1 ? 1 : g);
@@ -259,18 +266,33 @@ inline CuSplit* cu_split(int per32, hipStream_t caller) {
   return &cache[used - 1];
 }
 
-// joins both CU-masked streams back into the caller's stream on every return
+// Forks the caller's stream onto both CU-masked streams and joins them back:
+// by join(), or on any other return after the fork by the destructor, so no
+// error path leaves the caller's stream unordered against the forked kernels.
 struct SplitJoin {
-  CuSplit* cs = nullptr;
+  CuSplit* cs = nullptr;  // set between fork and join
   hipStream_t s = nullptr;
-  ~SplitJoin() {
-    if (cs) {
-      (void)hipEventRecord(cs->jh, cs->head);
-      (void)hipEventRecord(cs->jt, cs->tail);
-      (void)hipStreamWaitEvent(s, cs->jh, 0);
-      (void)hipStreamWaitEvent(s, cs->jt, 0);
-    }
+  // Both return the first failing call's error (wrap them in KGX_CHECK_HIP).
+  hipError_t fork(CuSplit* c, hipStream_t caller) {
+    hipError_t e = hipEventRecord(c->fork, caller);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->head, c->fork, 0);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->tail, c->fork, 0);
+    if (e != hipSuccess) return e;  // not armed: nothing to join
+    cs = c;
+    s = caller;
+    return hipSuccess;
   }
+  hipError_t join() {  // idempotent; every step is attempted
+    if (!cs) return hipSuccess;
+    CuSplit* c = cs;
+    cs = nullptr;
+    const hipError_t e[4] = {hipEventRecord(c->jh, c->head), hipEventRecord(c->jt, c->tail),
+                             hipStreamWaitEvent(s, c->jh, 0), hipStreamWaitEvent(s, c->jt, 0)};
+    for (hipError_t v : e)
+      if (v != hipSuccess) return v;
+    return hipSuccess;
+  }
+  ~SplitJoin() { (void)join(); }
 };
 
 

@@ -30,6 +30,8 @@
 
 #include "kgx_bf16x3.h"
 #include "kgx_internal.h"
+#include "kgx_mfma.h"
+#include "kgx_red.h"
 #include "kgx_vec.h"
 
 namespace kgx {
@@ -39,8 +41,6 @@ constexpr int kFin = 128;
 constexpr int kGroups = 16;       // rows per block iteration
 constexpr int kThreads = kGroups * 32;
 constexpr int kTileLd = kFin + 4;  // padded LDS row of the short-row kernel's f32 out tile
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The transform's operand split, the same in the main, short-row and tiny-row
 // kernels so their outputs stay bit-identical to each other: three bf16 planes
@@ -90,32 +90,12 @@ struct FusedArgs {
   bool cu_split;  // KGX_FUSED_CU_SPLIT (host side only)
 };
 
-// Source row of column c: x[c], or with TWO x2[c - n_x1] (one 64-bit select per
-// gathered row; a separate instantiation, so the one-table kernels keep their
-// register budget).
-template <bool TWO>
-__device__ __forceinline__ const float* gsrc(const FusedArgs& a, int32_t c) {
-  if constexpr (TWO) return (c >= a.n_x1 ? a.x2b : a.x) + row_off(c, a.ld_x);
-  return a.x + row_off(c, a.ld_x);
-}
-
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS ops
-// (lgkmcnt) but NOT for its outstanding global loads (vmcnt), unlike
-// __syncthreads(), so gathers prefetched for the next tile stay in flight.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // ---- three-way bf16 split of f32 operands (the "bf16x3" product) ---------
 // split3_a / split3_a_lo (kgx_bf16x3.h): x = hi + mid + lo; x*w is taken as the
 // six significant bf16 x bf16 products (dropped terms <= 2^-24 |x w|), each
 // exact in the MFMA's f32 accumulator, on v_mfma_f32_16x16x32_bf16 -- 16x the
 // per-clock rate of the f32-input MFMA.  Infinite / NaN aggregates follow
 // IEEE f32 products (non-finite aggregates go to the lo plane, kgx_bf16x3.h).
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
 
 // W's split B-fragments for this lane's output column n_col: k-step s (0..3)
 // of lane group q covers k = 32 q + 8 s + j (j = 0..7), so each A fragment is
@@ -126,7 +106,6 @@ __device__ __forceinline__ void load_w128(const Args& a, bool w_ok, int n_col, i
   auto wv = [&](int k) { return w_ok && (!NARROW || k < a.F_in) ? a.W[int64_t(k) * a.F_out + n_col] : 0.0f; };
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     u32x4_t ph, pm, pl;
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -146,8 +125,8 @@ __device__ __forceinline__ void load_w128(const Args& a, bool w_ok, int n_col, i
 // One k-step of a 16-row block on one accumulator, D^T += W^T x^T: the six
 // significant products of the split operands, small terms first (the tile's
 // planes ah / am / al)
-__device__ __forceinline__ f32x4 kstep_t(const bf16x8_t& wh, const bf16x8_t& wm, const bf16x8_t& wl,
-                                         const bf16x8_t& ah, const bf16x8_t& am, const bf16x8_t& al, f32x4 d) {
+__device__ __forceinline__ f32x4_t kstep_t(const bf16x8_t& wh, const bf16x8_t& wm, const bf16x8_t& wl,
+                                         const bf16x8_t& ah, const bf16x8_t& am, const bf16x8_t& al, f32x4_t d) {
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, al, d, 0, 0, 0);
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, ah, d, 0, 0, 0);
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, am, d, 0, 0, 0);
@@ -158,8 +137,8 @@ __device__ __forceinline__ f32x4 kstep_t(const bf16x8_t& wh, const bf16x8_t& wm,
 
 // The same products with the operands swapped, D += x W (the short-row
 // kernel's f32 out tile): same order, the same bits transposed
-__device__ __forceinline__ f32x4 kstep_n(const bf16x8_t& wh, const bf16x8_t& wm, const bf16x8_t& wl,
-                                         const bf16x8_t& ah, const bf16x8_t& am, const bf16x8_t& al, f32x4 d) {
+__device__ __forceinline__ f32x4_t kstep_n(const bf16x8_t& wh, const bf16x8_t& wm, const bf16x8_t& wl,
+                                         const bf16x8_t& ah, const bf16x8_t& am, const bf16x8_t& al, f32x4_t d) {
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wh, d, 0, 0, 0);
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wl, d, 0, 0, 0);
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, wm, d, 0, 0, 0);
@@ -199,38 +178,13 @@ __device__ __forceinline__ void split_row128(const float (&v)[4], bf16x4_t& ph, 
 // masks them; see kgx_zero_row (kgx_vec.h).
 template <bool TWO>
 __device__ __forceinline__ const float* gsrc_or_zero(const FusedArgs& a, bool present, int32_t c, int fg) {
-  return present ? gsrc<TWO>(a, c) + fg : kgx_zero_row + fg;
+  return present ? gather_src<TWO>(a, c) + fg : kgx_zero_row + fg;
 }
-
-template <int RED>
-struct Red {
-  static __device__ __forceinline__ float init() {
-    if constexpr (RED == KGX_MAX || RED == KGX_MIN) return -__builtin_inff();
-    return 0.0f;
-  }
-  static __device__ __forceinline__ float msg(float v) {
-    if constexpr (RED == KGX_MIN) return -v;
-    return v;
-  }
-  static __device__ __forceinline__ float combine(float a, float v) {
-    if constexpr (RED == KGX_MAX || RED == KGX_MIN) return amax_update(a, v);
-    return __fadd_rn(a, v);
-  }
-  static __device__ __forceinline__ float finish(float a, int32_t deg) {
-    if constexpr (RED == KGX_MEAN) return __fdiv_rn(a, fmaxf(ref_count_f32(deg), 1e-8f));
-    if constexpr (RED == KGX_MAX) return is_inf(a) ? 0.0f : a;
-    if constexpr (RED == KGX_MIN) {
-      const float r = -a;
-      return is_inf(r) ? 0.0f : r;
-    }
-    return a;
-  }
-};
 
 // NARROW: F_in < 128 or F_out not a multiple of 16 (masks compiled in only there)
 template <int RED, bool WEIGHTED, bool TWO, bool NARROW>
 __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedArgs a) {  // TWO: hold 4 waves per SIMD
-  using R = Red<RED>;
+  using R = RowRed<RED>;
   // gathers in flight per group: at F_in 128 (GCN, NS) 4 beat 6 and 8 with PF = U
   // (each cost occupancy) and U = 8 with PF = 2 (NS 8.90 -> 9.05-9.15 ms); the
   // narrow unweighted form (SAGE at C5: 50 edges per row on average) takes 6 in
@@ -329,7 +283,7 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
       }
       float v[B][4];
 #pragma unroll
-      for (int u = 0; u < B; ++u) vload<4>(v[u], gsrc<TWO>(a, c[u]) + fg);
+      for (int u = 0; u < B; ++u) vload<4>(v[u], gather_src<TWO>(a, c[u]) + fg);
 #pragma unroll
       for (int u = 0; u < B; ++u)
 #pragma unroll
@@ -372,8 +326,8 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
 
     if (mfma_wave) {
       const int m = wl & 15;
-      f32x4 d0 = {0.0f, 0.0f, 0.0f, 0.0f};
-      f32x4 d1 = {0.0f, 0.0f, 0.0f, 0.0f};  // two accumulation chains
+      f32x4_t d0 = {0.0f, 0.0f, 0.0f, 0.0f};
+      f32x4_t d1 = {0.0f, 0.0f, 0.0f, 0.0f};  // two accumulation chains
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) {
         const bf16x8_t ah = *reinterpret_cast<const bf16x8_t*>(&tile3[0][m][32 * q + 8 * s4]);
@@ -392,14 +346,9 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
       if (rr >= 0 && (!NARROW || c4 < a.F_out)) {
         float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + c4);
         const float4 b4 = *reinterpret_cast<const float4*>(&sbias[c4]);
-        float4 v = make_float4((d0[0] + d1[0]) + b4.x, (d0[1] + d1[1]) + b4.y, (d0[2] + d1[2]) + b4.z,
-                               (d0[3] + d1[3]) + b4.w);
-        if (a.accumulate) {
-          const float4 p = *dst;
-          v = make_float4(__fadd_rn(p.x, v.x), __fadd_rn(p.y, v.y), __fadd_rn(p.z, v.z), __fadd_rn(p.w, v.w));
-        }
-        if (a.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-        *dst = v;
+        const float4 v = make_float4((d0[0] + d1[0]) + b4.x, (d0[1] + d1[1]) + b4.y, (d0[2] + d1[2]) + b4.z,
+                                     (d0[3] + d1[3]) + b4.w);
+        store_out4(dst, v, a.accumulate, a.relu);
       }
     }
     lds_barrier();  // every wave is done with the planes and tile_row before the next tile's are written
@@ -423,7 +372,7 @@ constexpr int kShortRows = kGroups * kRPG;
 
 template <int RED, bool WEIGHTED, bool TWO, bool NARROW>
 __global__ __launch_bounds__(kThreads, 4) void spmm_gemm_short_kernel(FusedArgs a) {  // 4 waves per SIMD: two blocks per CU
-  using R = Red<RED>;
+  using R = RowRed<RED>;
   // split planes of the 32 aggregated rows; after the MFMAs the same bytes hold the f32 results
   __shared__ __attribute__((aligned(16))) short tile3[kFPlanes][kShortRows][kFin + 8];
   __shared__ int32_t tile_row[kShortRows];
@@ -510,7 +459,7 @@ __global__ __launch_bounds__(kThreads, 4) void spmm_gemm_short_kernel(FusedArgs 
           if constexpr (WEIGHTED) wt[u] = a.w[ee];
         }
 #pragma unroll
-        for (int u = 0; u < 2; ++u) vload<4>(v[u], gsrc<TWO>(a, c[u]) + fg);
+        for (int u = 0; u < 2; ++u) vload<4>(v[u], gather_src<TWO>(a, c[u]) + fg);
         // both loads stay unconditional: unweighted, hipcc otherwise sinks the
         // second (masked at the fold when n == 1) into an exec-masked branch
         asm volatile("" ::"v"(v[1][0]), "v"(v[1][1]), "v"(v[1][2]), "v"(v[1][3]));
@@ -550,11 +499,11 @@ __global__ __launch_bounds__(kThreads, 4) void spmm_gemm_short_kernel(FusedArgs 
       if (lane == 0) tile_row[tr] = row[r];
     }
     lds_barrier();
-    f32x4 d[kRPG];
+    f32x4_t d[kRPG];
     if (mfma_wave) {
       const int m = wl & 15;
 #pragma unroll
-      for (int rb = 0; rb < kRPG; ++rb) d[rb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int rb = 0; rb < kRPG; ++rb) d[rb] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) {
 #pragma unroll
@@ -581,13 +530,7 @@ __global__ __launch_bounds__(kThreads, 4) void spmm_gemm_short_kernel(FusedArgs 
       const int rr = tile_row[tr];
       if (rr >= 0 && f < a.F_out) {
         float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + f);
-        float4 v = *reinterpret_cast<const float4*>(&otile[tr][f]);
-        if (a.accumulate) {
-          const float4 p = *dst;
-          v = make_float4(__fadd_rn(p.x, v.x), __fadd_rn(p.y, v.y), __fadd_rn(p.z, v.z), __fadd_rn(p.w, v.w));
-        }
-        if (a.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-        *dst = v;
+        store_out4(dst, *reinterpret_cast<const float4*>(&otile[tr][f]), a.accumulate, a.relu);
       }
     }
   }
@@ -622,7 +565,7 @@ constexpr int tiny_rows() { return kTinyGroups * (NG == 1 ? kTinyRPG1 : kTinyRPG
 // degree <= 1 rest: the schedule is degree-descending, so each is a range).
 template <int RED, bool WEIGHTED, bool EXTRA, int NG, bool TWO, bool NARROW>  // EXTRA: pre_gin or agg_out (loads / stores under a row mask)
 __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedArgs a) {
-  using R = Red<RED>;
+  using R = RowRed<RED>;
   constexpr int kTinyRPG = NG == 1 ? kTinyRPG1 : kTinyRPG2;  // rows per group per tile
   constexpr int kTinyRows = kTinyGroups * kTinyRPG;
   __shared__ __attribute__((aligned(16))) short planes[2][kFPlanes][kTinyRows][kFin + 8];
@@ -647,9 +590,9 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
     for (int64_t i = 0; i <= my_tiles; ++i) {
       if (i >= 1 && mfma_wave) {
         const int b = int((i - 1) & 1);
-        f32x4 d[kTinyRPG];
+        f32x4_t d[kTinyRPG];
 #pragma unroll
-        for (int rb = 0; rb < kTinyRPG; ++rb) d[rb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int rb = 0; rb < kTinyRPG; ++rb) d[rb] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
 #pragma unroll
@@ -670,13 +613,8 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
           if (rr >= 0 && (!NARROW || c4 < a.F_out)) {
             float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + c4);
             const float4 b4 = *reinterpret_cast<const float4*>(&sbias[c4]);
-            float4 v = make_float4(d[rb][0] + b4.x, d[rb][1] + b4.y, d[rb][2] + b4.z, d[rb][3] + b4.w);
-            if (a.accumulate) {
-              const float4 p = *dst;
-              v = make_float4(__fadd_rn(p.x, v.x), __fadd_rn(p.y, v.y), __fadd_rn(p.z, v.z), __fadd_rn(p.w, v.w));
-            }
-            if (a.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-            *dst = v;
+            const float4 v = make_float4(d[rb][0] + b4.x, d[rb][1] + b4.y, d[rb][2] + b4.z, d[rb][3] + b4.w);
+            store_out4(dst, v, a.accumulate, a.relu);
           }
         }
       }
@@ -705,15 +643,14 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
       if constexpr (WEIGHTED) r.w[j] = a.tw[ec];
     }
   };
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  auto gather = [&](const Rec& r, f4 (&v)[kTinyRPG][NG]) {
+  auto gather = [&](const Rec& r, f32x4_t (&v)[kTinyRPG][NG]) {
 #pragma unroll
     for (int j = 0; j < kTinyRPG; ++j) {
-      v[j][0] = *reinterpret_cast<const f4*>(gsrc<TWO>(a, r.p[j].z) + fg);
-      if constexpr (NG == 2) v[j][1] = *reinterpret_cast<const f4*>(gsrc<TWO>(a, r.p[j].w) + fg);
+      v[j][0] = *reinterpret_cast<const f32x4_t*>(gather_src<TWO>(a, r.p[j].z) + fg);
+      if constexpr (NG == 2) v[j][1] = *reinterpret_cast<const f32x4_t*>(gather_src<TWO>(a, r.p[j].w) + fg);
     }
   };
-  auto produce = [&](int64_t i, const auto& c, const f4 (&v)[kTinyRPG][NG]) {
+  auto produce = [&](int64_t i, const auto& c, const f32x4_t (&v)[kTinyRPG][NG]) {
     const int b = int(i & 1);
 #pragma unroll
     for (int j = 0; j < kTinyRPG; ++j) {
@@ -771,12 +708,12 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
   };
   Rec ra, rb;
   Cur cur;
-  f4 v0[kTinyRPG][NG], v1[kTinyRPG][NG];
+  f32x4_t v0[kTinyRPG][NG], v1[kTinyRPG][NG];
   rec(0, rb);
   take(rb, cur);
   rec(1, ra);
   gather(rb, v0);
-  auto step = [&](int64_t i, Rec& rn, Rec& rfree, f4 (&vc)[kTinyRPG][NG], f4 (&vn)[kTinyRPG][NG]) {
+  auto step = [&](int64_t i, Rec& rn, Rec& rfree, f32x4_t (&vc)[kTinyRPG][NG], f32x4_t (&vn)[kTinyRPG][NG]) {
     rec(i + 2, rfree);  // tile i+2's records
     gather(rn, vn);     // tile i+1's rows
     produce(i, cur, vc);
@@ -793,7 +730,7 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
 // Split rows: combine chunk partials in order, finish, then out = v @ W + b (VALU).
 template <int RED, bool NARROW>
 __global__ __launch_bounds__(256) void spmm_gemm_fixup_kernel(FusedArgs a) {
-  using R = Red<RED>;
+  using R = RowRed<RED>;
   __shared__ float vrow[8][kFin];
   const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
   for (int64_t base = int64_t(blockIdx.x) * 8; base < a.n_split; base += int64_t(gridDim.x) * 8) {
@@ -846,8 +783,8 @@ __global__ __launch_bounds__(256) void spmm_gemm_fixup_kernel(FusedArgs a) {
 // measurement): the main kernel and the short + tiny launches on disjoint CU
 // sets (24 / 8 of every 32 CUs, CU-masked streams, kgx_internal.h cu_split).
 // Disjoint output rows; the tail launches' MFMA phases overlap the main
-// kernel's gathers instead of starting after it; joined before the hub
-// fix-up.  Measured and removed (tools/experiments/round5_fork_modes.patch):
+// kernel's gathers instead of starting after it; the hub fix-up follows the
+// main kernel on its stream, before the join.  Measured and removed (tools/experiments/round5_fork_modes.patch):
 // the tails forked onto an unmasked side stream (tiny only: NS 9.51-9.66 ms;
 // short + tiny: 8.89-8.94), and the main kernel capped to (den - 1) / den of
 // its grid with the tails in the slots left on every CU (8.82-8.86 at den 8;
@@ -857,21 +794,26 @@ inline int fused_fork_mode() {  // read per launch (tests switch it in-process)
   return h ? atoi(h) : 0;
 }
 
-template <int RED, bool W, bool TWO, bool NARROW>
-int launch_short(const FusedArgs& a, hipStream_t s, int cus = 0) {
-  int per_cu = 0;
-  auto k = spmm_gemm_short_kernel<RED, W, TWO, NARROW>;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kThreads, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-  const int64_t need = (a.n_short_end - a.n_long + kShortRows - 1) / kShortRows;
-  const int64_t full = int64_t(per_cu) * (cus > 0 ? cus : cu_count());
+// Grid of one launch: the blocks its work needs, at most `full` (the blocks
+// resident at once on its CU set), or under KGX_FUSED_SHARE_GPU (den - 1) / den
+// of them (shared_cap), so a concurrent collective's kernels (RCCL halo
+// all-to-all) and the side stream's packing are not starved.
+inline unsigned fused_grid(const FusedArgs& a, int64_t need, int64_t full) {
   const int64_t cap = a.share_gpu ? shared_cap(full) : full;
-  hipLaunchKernelGGL(k, dim3(unsigned(need < cap ? need : cap)), dim3(kThreads), 0, s, a);
+  return unsigned(need < cap ? need : cap);
+}
+
+template <int RED, bool W, bool TWO, bool NARROW>
+int launch_short(const FusedArgs& a, hipStream_t s, int cus) {
+  auto k = spmm_gemm_short_kernel<RED, W, TWO, NARROW>;
+  const int64_t need = (a.n_short_end - a.n_long + kShortRows - 1) / kShortRows;
+  hipLaunchKernelGGL(k, dim3(fused_grid(a, need, occupancy_blocks(k, kThreads, 2, cus))), dim3(kThreads), 0, s, a);
   KGX_CHECK_LAUNCH();
   return KGX_OK;
 }
 
 template <int RED, bool W, bool TWO, bool NARROW>
-int launch_tiny(const FusedArgs& a, hipStream_t s, int cus = 0) {
+int launch_tiny(const FusedArgs& a, hipStream_t s, int cus) {
   const bool extra = a.pre_gin || a.agg_out;
   for (int part = 0; part < 2; ++part) {  // one 1024-thread block per CU; degree-2 head, then the degree <= 1 rest
     FusedArgs b = a;
@@ -885,9 +827,7 @@ int launch_tiny(const FusedArgs& a, hipStream_t s, int cus = 0) {
                            : spmm_gemm_tiny_kernel<RED, W, false, 2, TWO, NARROW>);
     const int rows = part ? tiny_rows<1>() : tiny_rows<2>();
     const int64_t need = (b.n_tiny + rows - 1) / rows;
-    const int64_t full = cus > 0 ? cus : cu_count();
-    const int64_t cap = a.share_gpu ? shared_cap(full) : full;
-    hipLaunchKernelGGL(k, dim3(unsigned(need < cap ? need : cap)), dim3(kTinyThreads), 0, s, b);
+    hipLaunchKernelGGL(k, dim3(fused_grid(a, need, cus > 0 ? cus : cu_count())), dim3(kTinyThreads), 0, s, b);
     KGX_CHECK_LAUNCH();
   }
   return KGX_OK;
@@ -897,75 +837,40 @@ template <int RED, bool W, bool TWO = false, bool NARROW = false>
 int launch(const FusedArgs& a, hipStream_t s) {
   const int64_t work = a.items ? a.n_long : a.n_rows;
   const bool has_short = a.items && a.n_long < a.n_short_end;
-  const bool split = a.cu_split || fused_fork_mode() == 3;
-  if (split && work > 0 && ((a.tpack && a.n_tiny > 0) || has_short)) {
+  const bool has_tiny = a.tpack && a.n_tiny > 0;
+  hipStream_t sh = s, st = s;  // head (main kernel, hub fix-up) and tail (short + tiny rows) streams
+  int cus_h = 0, cus_t = 0;
+  SplitJoin join;
+  if ((a.cu_split || fused_fork_mode() == 3) && work > 0 && (has_tiny || has_short)) {
     // the main kernel on a CU-masked stream over 24 of every 32 CUs, the
     // short-row and tiny-row launches on another over the other 8 (cu_split)
     const char* e = getenv("KGX_FUSED_CU_SPLIT");  // tail CUs per 32 (default 8)
-    CuSplit* cs = cu_split(e ? atoi(e) : 8, s);
-    if (cs) {
-      SplitJoin join;
-      KGX_CHECK_HIP(hipEventRecord(cs->fork, s));
-      KGX_CHECK_HIP(hipStreamWaitEvent(cs->head, cs->fork, 0));
-      KGX_CHECK_HIP(hipStreamWaitEvent(cs->tail, cs->fork, 0));
-      join.cs = cs;
-      join.s = s;
-      int per_cu = 0;
-      auto k = spmm_gemm_kernel<RED, W, TWO, NARROW>;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kThreads, 0) != hipSuccess || per_cu <= 0)
-        per_cu = 2;
-      const int64_t need = (work + kGroups - 1) / kGroups;
-      const int64_t full = int64_t(per_cu) * cs->n_head;
-      const int64_t cap = a.share_gpu ? shared_cap(full) : full;
-      hipLaunchKernelGGL(k, dim3(unsigned(need < cap ? need : cap)), dim3(kThreads), 0, cs->head, a);
-      KGX_CHECK_LAUNCH();
-      if (a.items && a.n_split > 0) {
-        // the hub fix-up reads only the main kernel's partials and writes only split rows:
-        // on the head's CUs right after it, hidden behind the longer tail leg
-        const int64_t blocks = (a.n_split + 7) / 8;
-        auto fk = spmm_gemm_fixup_kernel<RED, NARROW>;
-        hipLaunchKernelGGL(fk, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(256), 0, cs->head, a);
-        KGX_CHECK_LAUNCH();
-      }
-      if (has_short && launch_short<RED, W, TWO, NARROW>(a, cs->tail, cs->n_tail) != KGX_OK) return KGX_ERR_HIP;
-      if (a.tpack && a.n_tiny > 0 && launch_tiny<RED, W, TWO, NARROW>(a, cs->tail, cs->n_tail) != KGX_OK)
-        return KGX_ERR_HIP;
-      join.cs = nullptr;
-      KGX_CHECK_HIP(hipEventRecord(cs->jh, cs->head));
-      KGX_CHECK_HIP(hipEventRecord(cs->jt, cs->tail));
-      KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jh, 0));
-      KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jt, 0));
-      return KGX_OK;
+    if (CuSplit* cs = cu_split(e ? atoi(e) : 8, s)) {
+      KGX_CHECK_HIP(join.fork(cs, s));
+      sh = cs->head;
+      st = cs->tail;
+      cus_h = cs->n_head;
+      cus_t = cs->n_tail;
     }
   }
+  // (both named here: the code object keeps its order of kernels, main, fix-up, short, tiny)
+  auto k = spmm_gemm_kernel<RED, W, TWO, NARROW>;
+  auto fk = spmm_gemm_fixup_kernel<RED, NARROW>;
   if (work > 0) {
-    static int cus = 0;
-    if (cus == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    }
-    int per_cu = 0;
-    auto k = spmm_gemm_kernel<RED, W, TWO, NARROW>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kThreads, 0) != hipSuccess || per_cu <= 0)
-      per_cu = 2;
     const int64_t need = (work + kGroups - 1) / kGroups;
-    // KGX_FUSED_SHARE_GPU: leave 1/den of the block slots free (share_den(),
-    // default a sixteenth) so a concurrent collective's kernels (RCCL halo
-    // all-to-all) and the side stream's packing are not starved
-    const int64_t cap = a.share_gpu ? shared_cap(int64_t(per_cu) * cus) : int64_t(per_cu) * cus;
-    hipLaunchKernelGGL(k, dim3(unsigned(need < cap ? need : cap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(k, dim3(fused_grid(a, need, occupancy_blocks(k, kThreads, 2, cus_h))), dim3(kThreads), 0, sh, a);
     KGX_CHECK_LAUNCH();
   }
-  if (has_short && launch_short<RED, W, TWO, NARROW>(a, s) != KGX_OK) return KGX_ERR_HIP;
-  if (a.tpack && a.n_tiny > 0 && launch_tiny<RED, W, TWO, NARROW>(a, s) != KGX_OK) return KGX_ERR_HIP;
+  if (has_short && launch_short<RED, W, TWO, NARROW>(a, st, cus_t) != KGX_OK) return KGX_ERR_HIP;
+  if (has_tiny && launch_tiny<RED, W, TWO, NARROW>(a, st, cus_t) != KGX_OK) return KGX_ERR_HIP;
   if (a.items && a.n_split > 0) {
+    // the hub fix-up reads only the main kernel's partials and writes only split rows: behind
+    // the main kernel on its stream -- split, on the head's CUs, hidden behind the longer tail leg
     const int64_t blocks = (a.n_split + 7) / 8;
-    auto fk = spmm_gemm_fixup_kernel<RED, NARROW>;
-    hipLaunchKernelGGL(fk, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(fk, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(256), 0, sh, a);
     KGX_CHECK_LAUNCH();
   }
+  KGX_CHECK_HIP(join.join());
   return KGX_OK;
 }
 
@@ -1071,7 +976,7 @@ extern "C" int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_
   a.x = x;
   a.ld_x = ld_x;
   a.n_x1 = x2 ? int32_t(n_x1) : INT32_MAX;
-  // x2 - n_x1 * ld_x as an address (modular): gsrc adds row_off(c) for c >= n_x1
+  // x2 - n_x1 * ld_x as an address (modular): gather_src adds row_off(c) for c >= n_x1
   a.x2b = x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(x2) -
                                                uintptr_t(n_x1) * uintptr_t(ld_x) * sizeof(float))
              : x;

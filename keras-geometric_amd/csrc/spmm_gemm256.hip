@@ -26,6 +26,7 @@
 
 #include "kgx_bf16x3.h"
 #include "kgx_internal.h"
+#include "kgx_mfma.h"
 #include "kgx_red.h"
 #include "kgx_vec.h"
 
@@ -44,11 +45,6 @@ constexpr int kSteps = kF / 32;    // k-steps of 32 per MFMA chain
 // 2^-20.4-accurate: outside the f32 contract) and the cost-decomposition
 // builds are kept out of this file: tools/experiments/round4_variants.patch.
 constexpr int kPlanes = 3;  // activation planes per tile row
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 struct F256Args {
   const int32_t* rowptr;
@@ -86,22 +82,6 @@ struct F256Args {
   int32_t n_x1;
   bool cu_split;  // KGX_FUSED_CU_SPLIT (host side only)
 };
-
-// Source row of column c: x[c], or with TWO x2[c - n_x1].  Root rows (pre_gin's
-// x_i) are always rows of x.
-template <bool TWO>
-__device__ __forceinline__ const float* gsrc256(const F256Args& a, int32_t c) {
-  if constexpr (TWO) return (c >= a.n_x1 ? a.x2b : a.x) + row_off(c, a.ld_x);
-  return a.x + row_off(c, a.ld_x);
-}
-
-// workgroup barrier for LDS hand-offs only (lgkmcnt, not vmcnt): gathers
-// prefetched for the next tile stay in flight across it
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // W fragments of this wave's two 16-column blocks, k permuted: k-step s of lane
 // group q covers k = 64 q + 8 s + j (j = 0..7), so each x fragment is 8
@@ -168,7 +148,7 @@ __device__ __forceinline__ void transform_tile(const F256Args& a, const short (*
   const int cl = wl & 15, q = wl >> 4;
   const bool mf0 = 32 * wave < a.F_out, mf1 = 32 * wave + 16 < a.F_out;
   if (!mf0) return;
-  f32x4 d[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+  f32x4_t d[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
 #pragma unroll
   for (int s = 0; s < kSteps; ++s) {
     const int kk = 64 * q + 8 * s;
@@ -195,13 +175,7 @@ __device__ __forceinline__ void transform_tile(const F256Args& a, const short (*
     const int c4 = 32 * wave + 16 * i + 4 * q;
     float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + c4);
     const float4 b4 = *reinterpret_cast<const float4*>(&sbias[c4]);
-    float4 v = make_float4(d[i][0] + b4.x, d[i][1] + b4.y, d[i][2] + b4.z, d[i][3] + b4.w);
-    if (a.accumulate) {
-      const float4 p = *dst;
-      v = make_float4(__fadd_rn(p.x, v.x), __fadd_rn(p.y, v.y), __fadd_rn(p.z, v.z), __fadd_rn(p.w, v.w));
-    }
-    if (a.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-    *dst = v;
+    store_out4(dst, make_float4(d[i][0] + b4.x, d[i][1] + b4.y, d[i][2] + b4.z, d[i][3] + b4.w), a.accumulate, a.relu);
   }
 }
 
@@ -274,7 +248,7 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_kernel(F256Args a) {
     for (int r = 0; r < 2; ++r)
 #pragma unroll
       for (int u = 0; u < PF; ++u)
-        if (u < pn[r]) vload<4>(pv[r][u], gsrc256<TWO>(a, c[r][u]) + f);
+        if (u < pn[r]) vload<4>(pv[r][u], gather_src<TWO>(a, c[r][u]) + f);
     if (a.pre_gin) {  // wave-uniform; clamped rows, unconditional per lane
 #pragma unroll
       for (int r = 0; r < 2; ++r) vload<4>(px[r], a.x + int64_t(row[r] >= 0 ? row[r] : 0) * a.ld_x + f);
@@ -312,7 +286,7 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_kernel(F256Args a) {
       }
       float v[B][4];
 #pragma unroll
-      for (int u = 0; u < B; ++u) vload<4>(v[u], gsrc256<TWO>(a, c[u]) + f);
+      for (int u = 0; u < B; ++u) vload<4>(v[u], gather_src<TWO>(a, c[u]) + f);
 #pragma unroll
       for (int u = 0; u < B; ++u)
 #pragma unroll
@@ -340,8 +314,8 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_kernel(F256Args a) {
       float v[2][U][4];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        vload<4>(v[0][u], gsrc256<TWO>(a, c[0][u]) + f);
-        vload<4>(v[1][u], gsrc256<TWO>(a, c[1][u]) + f);
+        vload<4>(v[0][u], gather_src<TWO>(a, c[0][u]) + f);
+        vload<4>(v[1][u], gather_src<TWO>(a, c[1][u]) + f);
       }
 #pragma unroll
       for (int r = 0; r < 2; ++r)
@@ -472,8 +446,8 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_tiny2_kernel(F256Arg
         pw[r][0] = rw[B][r].x;
         pw[r][1] = rw[B][r].y;
       }
-      vload<4>(pv[r][0], gsrc256<TWO>(a, rec[B][r].z) + f);
-      vload<4>(pv[r][1], gsrc256<TWO>(a, rec[B][r].w) + f);
+      vload<4>(pv[r][0], gather_src<TWO>(a, rec[B][r].z) + f);
+      vload<4>(pv[r][1], gather_src<TWO>(a, rec[B][r].w) + f);
       if constexpr (GIN) vload<4>(px[r], a.x + row_off(rec[B][r].x, a.ld_x) + f);
     }
   };
@@ -504,7 +478,7 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_tiny2_kernel(F256Arg
     const short(*t3)[kRows][kLd] = tile3[pb];
     const bool mf0 = FASTS || 32 * wave < a.F_out, mf1 = FASTS || 32 * wave + 16 < a.F_out;
     if (!mf0) return;
-    f32x4 d[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    f32x4_t d[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
 #pragma unroll
     for (int st = 0; st < kSteps; ++st) {
       const int kk = 64 * q + 8 * st;
@@ -532,13 +506,8 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_gemm256_tiny2_kernel(F256Arg
       const int c4 = 32 * wave + 16 * i + 4 * q;
       float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + c4);
       const float4 b4 = *reinterpret_cast<const float4*>(&sbias[c4]);
-      float4 v = make_float4(d[i][0] + b4.x, d[i][1] + b4.y, d[i][2] + b4.z, d[i][3] + b4.w);
-      if (!FASTS && a.accumulate) {
-        const float4 p = *dst;
-        v = make_float4(__fadd_rn(p.x, v.x), __fadd_rn(p.y, v.y), __fadd_rn(p.z, v.z), __fadd_rn(p.w, v.w));
-      }
-      if (a.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-      *dst = v;
+      store_out4(dst, make_float4(d[i][0] + b4.x, d[i][1] + b4.y, d[i][2] + b4.z, d[i][3] + b4.w),
+                 !FASTS && a.accumulate, a.relu);
     }
   };
   // period t (parity p): tile t's MFMAs; tile t+1 folded into buffer p^1; tile
@@ -645,9 +614,7 @@ __global__ __launch_bounds__(256) void spmm_gemm256_fixup_kernel(F256Args a) {
 
 template <typename K>
 unsigned grid256(K k, int64_t tiles, int cus = 0) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kThreads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
-  const int64_t cap = int64_t(per_cu) * (cus > 0 ? cus : cu_count());
+  const int64_t cap = occupancy_blocks(k, kThreads, 1, cus);
   return unsigned(tiles < cap ? tiles : cap);
 }
 
@@ -686,11 +653,7 @@ int launch256(const F256Args& a, hipStream_t s) {
   const int per32 = (a.cu_split && a.tpack && a.n_tiny > 0 && work > 0) ? cu_split_per32() : 0;
   if (per32) {
     if (CuSplit* cs = cu_split(per32, s)) {
-      KGX_CHECK_HIP(hipEventRecord(cs->fork, s));
-      KGX_CHECK_HIP(hipStreamWaitEvent(cs->head, cs->fork, 0));
-      KGX_CHECK_HIP(hipStreamWaitEvent(cs->tail, cs->fork, 0));
-      join.cs = cs;
-      join.s = s;
+      KGX_CHECK_HIP(join.fork(cs, s));
       sh = cs->head;
       st = cs->tail;
       cus_h = cs->n_head;
@@ -735,14 +698,7 @@ int launch256(const F256Args& a, hipStream_t s) {
     hipLaunchKernelGGL(k, dim3(grid256(k, (b.n_work + kRows - 1) / kRows, cus_t)), dim3(kThreads), 0, st, b);
     KGX_CHECK_LAUNCH();
   }
-  if (join.cs) {  // the fix-up reads the long launch's partials: join first
-    CuSplit* cs = join.cs;
-    join.cs = nullptr;
-    KGX_CHECK_HIP(hipEventRecord(cs->jh, cs->head));
-    KGX_CHECK_HIP(hipEventRecord(cs->jt, cs->tail));
-    KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jh, 0));
-    KGX_CHECK_HIP(hipStreamWaitEvent(s, cs->jt, 0));
-  }
+  KGX_CHECK_HIP(join.join());  // the fix-up reads the long launch's partials: join first
   if (a.items && a.n_split > 0) {
     const int64_t blocks = (a.n_split + 3) / 4;
     hipLaunchKernelGGL(spmm_gemm256_fixup_kernel<RED>, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
@@ -829,7 +785,7 @@ extern "C" int kgx_spmm_gemm_f256_ex(int reduce, const int32_t* rowptr, const in
   a.gin_scale = gin_scale;
   a.cu_split = (flags & KGX_FUSED_CU_SPLIT) != 0;
   a.n_x1 = x2 ? int32_t(n_x1) : INT32_MAX;
-  // x2 - n_x1 * ld_x as an address (modular): gsrc256 adds row_off(c) for c >= n_x1
+  // x2 - n_x1 * ld_x as an address (modular): gather_src adds row_off(c) for c >= n_x1
   a.x2b = x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(x2) -
                                                uintptr_t(n_x1) * uintptr_t(ld_x) * sizeof(float))
              : nullptr;

@@ -351,37 +351,33 @@ def _partial_width(x: torch.Tensor) -> int:
     return F256 if x.shape[1] == F256 else 128
 
 
-def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale, save_agg,
-                    relu=False, n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None):
-    x, w, W, bias, x2 = _f32c(x), _f32c(w), _f32c(W), _f32c(bias), _f32c(x2)
-    dev = nat.require_device(x, rowptr, rows, idx, w, W, bias, items, split, x2)
+def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, flags, gin_scale,
+                  allow_split, n_long, tpack, tw, n_short_end, n_tiny2, dev):
+    """One fused aggregate -> transform launch into out (n_dst > 0 rows), and into
+    agg, when given, the aggregated rows before the transform: the hub partials,
+    the 256- / 128-wide dispatch, the CU-split decision and the native call.
+    allow_split is off for the training forward's saved-aggregate launch: its
+    tail launches also store the aggregated rows (the EXTRA instantiations), and
+    split it measured slower (NS training step 23.1 -> 25.0 ms, profiles/r05/train/)."""
     n_dst = rowptr.numel() - 1
-    F_out = W.shape[1]
-    out = torch.empty((n_dst, F_out), dtype=torch.float32, device=dev)
-    agg = torch.empty((n_dst if save_agg else 0, x.shape[1]), dtype=torch.float32, device=dev)
-    if n_dst == 0:
-        return out, agg
     n_items = 0 if items is None else items.shape[0]
     n_split = 0 if split is None else split.shape[0]
     partials = None
     if items is not None and n_split > 0:
         partials = torch.empty((n_slots, _partial_width(x)), dtype=torch.float32, device=dev)
-    flags = int(pre_gin) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0) | (nat.FUSED_RELU if relu else 0)
+    allow_split = allow_split and items is not None
     if x.shape[1] == F256:
-        if tpack is not None and items is not None and not save_agg and _split_allowed(dev) and \
+        if tpack is not None and allow_split and _split_allowed(dev) and \
                 _f256_cu_split(idx.numel(), n_items - (n_short_end if n_short_end >= 0 else n_items)):
             flags |= nat.FUSED_CU_SPLIT
             _count_cu_split()
         _f256_call(reduce, rowptr, rows, n_dst, items, n_items, split, n_split, idx, w, x, x2, W, bias, flags,
-                   gin_scale, out, partials, agg if save_agg else None, dev, tpack, tw, n_short_end, n_long)
-        return out, agg
+                   gin_scale, out, partials, agg, dev, tpack, tw, n_short_end, n_long)
+        return
     n_long = n_items if n_long < 0 or n_long > n_items else n_long
     n_se, tpack, tw, n_tiny2 = _tiny_abi(items, n_items, n_long, tpack, tw if w is not None else None, n_short_end,
                                          n_tiny2)
-    # not for the training forward's saved-aggregate launch: its tail launches also store the
-    # aggregated rows (the EXTRA instantiations), and split it measured slower (NS training step
-    # 23.1 -> 25.0 ms, profiles/r05/train/)
-    if items is not None and not save_agg and _split_allowed(dev) and _fused_cu_split(idx.numel(), n_items - n_long):
+    if allow_split and _split_allowed(dev) and _fused_cu_split(idx.numel(), n_items - n_long):
         flags |= nat.FUSED_CU_SPLIT
         _count_cu_split()
     x2p, n_x1 = _x2_args(x, x2)
@@ -389,13 +385,26 @@ def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, b
         nat.lib().kgx_spmm_gemm_ex3(
             reduce, nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, n_long, n_se, nat.ptr(tpack),
             nat.ptr(tw), n_tiny2, nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), F_out, nat.ptr(bias),
-            flags, float(gin_scale), nat.ptr(out), out.stride(0),
-            nat.ptr(partials),
-            nat.ptr(agg) if save_agg else None, agg.stride(0) if save_agg else 0, nat.stream(dev),
+            nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), W.shape[1],
+            nat.ptr(bias), flags, float(gin_scale), nat.ptr(out), out.stride(0), nat.ptr(partials),
+            nat.ptr(agg), agg.stride(0) if agg is not None else 0, nat.stream(dev),
         ),
         "kgx_spmm_gemm",
     )
+
+
+def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale, save_agg,
+                    relu=False, n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None):
+    x, w, W, bias, x2 = _f32c(x), _f32c(w), _f32c(W), _f32c(bias), _f32c(x2)
+    dev = nat.require_device(x, rowptr, rows, idx, w, W, bias, items, split, x2)
+    n_dst = rowptr.numel() - 1
+    out = torch.empty((n_dst, W.shape[1]), dtype=torch.float32, device=dev)
+    agg = torch.empty((n_dst if save_agg else 0, x.shape[1]), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return out, agg
+    flags = int(pre_gin) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0) | (nat.FUSED_RELU if relu else 0)
+    _fused_launch(out, agg if save_agg else None, x, x2, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias,
+                  flags, gin_scale, not save_agg, n_long, tpack, tw, n_short_end, n_tiny2, dev)
     return out, agg
 
 
@@ -502,37 +511,9 @@ def spmm_gemm_acc_(
         raise ValueError(f"spmm_gemm_acc_: out must be float32 [{n_dst}, {W.shape[1]}] with unit column stride")
     if n_dst == 0:
         return
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    partials = None
-    if items is not None and n_split > 0:
-        partials = torch.empty((n_slots, _partial_width(x)), dtype=torch.float32, device=dev)
-    if x.shape[1] == F256:
-        if tpack is not None and items is not None and _split_allowed(dev) and \
-                _f256_cu_split(idx.numel(), n_items - (n_short_end if n_short_end >= 0 else n_items)):
-            flags |= nat.FUSED_CU_SPLIT
-            _count_cu_split()
-        _f256_call(reduce, rowptr, rows, n_dst, items, n_items, split, n_split, idx, w, x, x2, W, bias,
-                   (nat.FUSED_ACCUMULATE if accumulate else 0) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0) | flags,
-                   gin_scale, out, partials, None, dev, tpack, tw, n_short_end, n_long)
-        return
-    n_long = n_items if n_long < 0 or n_long > n_items else n_long
-    n_se, tpack, tw, n_tiny2 = _tiny_abi(items, n_items, n_long, tpack, tw if w is not None else None, n_short_end,
-                                         n_tiny2)
-    if items is not None and _split_allowed(dev) and _fused_cu_split(idx.numel(), n_items - n_long):
-        flags |= nat.FUSED_CU_SPLIT
-        _count_cu_split()
-    x2p, n_x1 = _x2_args(x, x2)
-    nat.check(
-        nat.lib().kgx_spmm_gemm_ex3(
-            reduce, nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, n_long, n_se, nat.ptr(tpack),
-            nat.ptr(tw), n_tiny2, nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), W.shape[1],
-            nat.ptr(bias), (nat.FUSED_ACCUMULATE if accumulate else 0) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0) | flags,
-            float(gin_scale), nat.ptr(out), out.stride(0), nat.ptr(partials), None, 0, nat.stream(dev),
-        ),
-        "kgx_spmm_gemm",
-    )
+    flags |= (nat.FUSED_ACCUMULATE if accumulate else 0) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0)
+    _fused_launch(out, None, x, x2, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, flags, gin_scale,
+                  True, n_long, tpack, tw, n_short_end, n_tiny2, dev)
 
 
 @spmm_gemm_acc_.register_fake

@@ -148,6 +148,49 @@ def test_fused_fork_bit_identical(dev, fork, monkeypatch):
     fused_ref.check(y1, g, fused_ref.reference(g, x, W, "sum", True, b), f"fork {fork}")
 
 
+def test_fused_fork_hub_fixup_bit_identical(dev, monkeypatch):
+    """A schedule with split hub rows, short rows and tiny records all at once:
+    under the CU split the hub fix-up runs behind the main kernel on the head
+    stream, before the join, beside the short + tiny launches on the tail
+    stream.  Same bits as the one-stream order, for the returning launch and
+    for the accumulate form into a non-zero out, and the next op on the
+    caller's stream sees every row (hub rows included)."""
+    n = 60_000
+    g, ei = _graph(dev, self_loops=True, gcn_norm=True)
+    if g.split.shape[0] == 0:  # no hub in the R-MAT draw: give node 0 four chunks' worth of in-edges
+        m = 4 * g.split_len
+        assert m < n
+        src = torch.cat([ei[0], torch.arange(m, device=dev, dtype=ei.dtype)])
+        dst = torch.cat([ei[1], torch.zeros(m, device=dev, dtype=ei.dtype)])
+        g = G.build_csr(src.contiguous(), dst.contiguous(), n, n, self_loops=True, gcn_norm=True)
+    assert g.split.shape[0] >= 1 and g.n_split == g.split.shape[0]
+    _with_tiny(g)
+    tiny_start = g._kgx_tiny[2]
+    assert 0 < g.n_long < tiny_start < g.n_items  # main items, short rows and tiny records
+    gen = torch.Generator(device=dev).manual_seed(10)
+    x = torch.randn(n, 128, device=dev, generator=gen)
+    W = torch.randn(128, 128, device=dev, generator=gen) * 0.1
+    b = torch.randn(128, device=dev, generator=gen)
+    acc0 = torch.randn(n, 128, device=dev, generator=gen)
+    hub = g.split[:, 0].long()
+    res = {}
+    for fork in ("0", "3"):
+        monkeypatch.setenv("KGX_FUSED_FORK", fork)
+        y = kops.aggregate_transform(g, x, W, "sum", weighted=True, bias=b)
+        s = y.sum(1)  # consumed right away on the same stream
+        acc = acc0.clone()
+        with torch.no_grad():
+            kops.aggregate_transform(g, x, W, "sum", weighted=True, bias=b, out=acc)  # spmm_gemm_acc_, accumulate
+        sa = acc.sum(1)
+        res[fork] = (y, s, acc, sa)
+    for k, name in enumerate(("y", "sum(y)", "acc", "sum(acc)")):
+        torch.testing.assert_close(res["3"][k], res["0"][k], rtol=0, atol=0, msg=name)
+    y, s, acc, sa = res["3"]
+    torch.testing.assert_close(s, y.sum(1), rtol=0, atol=0)  # the early reduction saw the final rows
+    torch.testing.assert_close(sa, acc.sum(1), rtol=0, atol=0)
+    assert bool((acc[hub] != acc0[hub]).any(1).all())  # the fix-up wrote every hub row
+
+
 @pytest.mark.parametrize("weighted", [True, False])
 def test_device_records_equal_host_restatement(weighted, dev):
     """kgx_tiny_pack / kgx_schedule_suffixes (the device build of the tail
