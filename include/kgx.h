@@ -598,6 +598,87 @@ int kgx_select_dst_range(const int32_t* src, const int32_t* dst, int64_t n,
                          kgx_stream_t stream);
 int kgx_select_workspace_bytes(int64_t n, size_t* bytes);
 
+/* ---------------------------------------------------------------------------
+ * Neighbour sampling for mini-batch GraphSAGE training (no reference
+ * counterpart: the reference trains full-batch; the semantics are those of
+ * PyG's NeighborLoader without replacement).
+ *
+ * kgx_sample_neighbors: one hop of fan-out sampling over a destination CSR
+ * (rowptr[n_rows+1], col, eid of kgx_csr_build).  Row i of the result belongs
+ * to seeds[i] (int32 row ids) and holds min(deg(seeds[i]), fanout) edges;
+ * fanout = -1 takes every neighbour.
+ *   out_rowptr[n_seeds+1]  offsets of the rows (a count kernel + exclusive scan)
+ *   out_src[cap]           global source id of each sampled edge
+ *   out_eid[cap]           input edge id of each sampled edge (to carry edge
+ *                          weights or attributes along)
+ * cap >= n_seeds * fanout; with fanout = -1 cap must cover the seeds' total
+ * degree (else KGX_ERR_ARG after the sync, and out_src / out_eid are not
+ * written).  A row of degree d <= fanout (or fanout = -1) is taken whole, in
+ * CSR order.  A row of degree d > fanout = k takes the k distinct CSR slots
+ * pi(0), ..., pi(k-1), emitted in that order, pi(t) = (phi(t) + rot) mod d,
+ * phi = a 4-round Feistel permutation of [0, 2^(2 hb)), hb =
+ * ceil(ceil_log2(d) / 2) bits per half (a superset smaller than 4 d),
+ * cycle-walked into [0, d):
+ *   round i:  (L, R) <- (R, L ^ (splitmix64(key[i] ^ R) & (2^hb - 1))),
+ *   x = (L << hb) | R, repeated while the result is >= d.
+ * The keys and the rotation depend on (seed, hop, the row's global id) only
+ * (uint64 arithmetic modulo 2^64, splitmix64 as in kgx_rmat_edges):
+ *   hs     = splitmix64(seed ^ splitmix64(uint64(uint32(hop))))
+ *   rs     = splitmix64(hs ^ uint64(row))
+ *   key[i] = splitmix64(rs + i),  i = 0..3
+ *   rot    = ((splitmix64(rs + 4) >> 32) * d) >> 32          (in [0, d))
+ * (the rotation makes every slot of a row equally likely: four Feistel rounds
+ * on halves of one or two bits are biased even under ideal keys),
+ * so a node's sample is independent of the batch it appears in, of its
+ * position in `seeds`, of the grid size and of the device; one lane computes
+ * each output slot and no atomic decides an output value (tests/sampling_ref.py
+ * restates it in numpy, bit for bit).  Sampling is over CSR slots: an edge the
+ * input lists twice has two slots and can be drawn once per copy.
+ * info[4] (host): sampled edges (= out_rowptr[n_seeds]), seeds out of range,
+ * 0, 0.  Synchronises `stream` once, like kgx_csr_build.
+ * Errors before any device call (KGX_ERR_ARG): null pointers, fanout == 0 or
+ * < -1, n_seeds < 0, n_seeds * fanout >= 2^31, cap < n_seeds * fanout, a
+ * workspace smaller than kgx_sample_workspace_bytes(n_seeds).  n_seeds == 0:
+ * KGX_OK, nothing launched.  A seed outside [0, n_rows) is counted on the
+ * device and reported as KGX_ERR_INDEX after the sync (its row is empty and
+ * nothing is read for it).
+ *
+ * kgx_relabel_frontier: compacts one hop into local ids.
+ *   nodes[n_known]      the node list so far (global ids, seeds first, distinct)
+ *   frontier[n_f]       the rows just expanded: frontier[i] is row i of
+ *                       out_rowptr (hop 0: the seeds); every entry is in nodes
+ *   out_rowptr, out_src the hop's result, n_edges = out_rowptr[n_f]
+ *   map[n_nodes]        caller-owned int32 scratch: every entry -1 on entry,
+ *                       and -1 again on return (also on the errors below)
+ * Outputs:
+ *   new_nodes[n_edges]  (capacity) the sampled sources not in nodes, each once,
+ *                       in ascending global id (radix sort, adjacent-unique
+ *                       flags, scan, select); local id = n_known + rank
+ *   src_local[n_edges]  local id of out_src[e]
+ *   dst_local[n_edges]  local id of the frontier row edge e belongs to
+ * The map is written for nodes at the start (map[nodes[i]] = i) and reset for
+ * nodes and new_nodes at the end: the work is O(n_known + n_edges), never
+ * O(n_nodes).  info[4] (host): new nodes, duplicate entries of nodes, ids out
+ * of range, 0.  Synchronises `stream` once.  Duplicate ids in nodes are found
+ * on the device (every entry re-reads the map after all have written it) and
+ * reported as KGX_ERR_ARG after the sync; an id outside [0, n_nodes) in nodes,
+ * frontier or out_src as KGX_ERR_INDEX (it is never used as an index).
+ * Errors before any device call (KGX_ERR_ARG): null pointers, negative sizes,
+ * n_known + n_edges >= 2^31, edges without a frontier row, a workspace smaller
+ * than kgx_relabel_workspace_bytes(n_edges, n_nodes).
+ * ------------------------------------------------------------------------- */
+int kgx_sample_workspace_bytes(int64_t n_seeds, size_t* bytes);
+int kgx_sample_neighbors(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t n_rows,
+                         const int32_t* seeds, int64_t n_seeds, int fanout, uint64_t seed, int hop,
+                         int32_t* out_rowptr, int32_t* out_src, int32_t* out_eid, int64_t cap,
+                         void* workspace, size_t workspace_bytes, int64_t* info, kgx_stream_t stream);
+int kgx_relabel_workspace_bytes(int64_t n_edges, int64_t n_nodes, size_t* bytes);
+int kgx_relabel_frontier(const int32_t* nodes, int64_t n_known, const int32_t* frontier, int64_t n_f,
+                         const int32_t* out_rowptr, const int32_t* out_src, int64_t n_edges,
+                         int32_t* map, int64_t n_nodes, int32_t* new_nodes, int32_t* src_local,
+                         int32_t* dst_local, void* workspace, size_t workspace_bytes, int64_t* info,
+                         kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from .layers import (
     Set2Set,
     set_random_seed,
 )
+from .sampling import NeighborSampler, SampledSubgraph
 from .utils import GraphData, add_self_loops, batch_graphs, compute_gcn_normalization
 
 __version__ = "0.1.0"
@@ -35,7 +36,9 @@ __all__ = [
     "GlobalPooling",
     "GraphData",
     "MessagePassing",
+    "NeighborSampler",
     "SAGEConv",
+    "SampledSubgraph",
     "Set2Set",
     "add_self_loops",
     "batch_graphs",

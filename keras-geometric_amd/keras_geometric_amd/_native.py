@@ -150,6 +150,18 @@ _SIGNATURES = {
         _i32p, _i32p, _i64, _i64, _i64, _i32p, _i32p,
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
     ],
+    "kgx_sample_workspace_bytes": [_i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_sample_neighbors": [
+        _i32p, _i32p, _i32p, _i64, _i32p, _i64, _int, ctypes.c_uint64, _int,
+        _i32p, _i32p, _i32p, _i64,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+    ],
+    "kgx_relabel_workspace_bytes": [_i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_relabel_frontier": [
+        _i32p, _i64, _i32p, _i64, _i32p, _i32p, _i64,
+        _i32p, _i64, _i32p, _i32p, _i32p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+    ],
 }
 _RESTYPES = {"kgx_last_error": ctypes.c_char_p}
 

@@ -1,0 +1,201 @@
+"""Neighbour sampling for mini-batch GraphSAGE training, on the device.
+
+`NeighborSampler` draws a fan-out sample around a batch of seed nodes
+(kgx_sample_neighbors, one launch group per hop) and compacts it into a small
+graph with local ids (kgx_relabel_frontier); the existing layers run on it,
+with autograd, like on any other edge_index:
+
+    sampler = NeighborSampler(edge_index, num_nodes, fanouts=[15, 10], seed=0)
+    sub = sampler.sample(batch_ids, epoch=e)
+    out = layer([sub.gather(x), sub.edge_index])[: sub.n_seeds]
+
+The reference has no sampler (it trains full-batch); the semantics are those of
+PyG's NeighborLoader without replacement: hop 0 expands the seeds, hop h > 0
+expands exactly the nodes hop h - 1 added, every node is expanded at most once.
+The sample is counter based: a node's neighbours depend on (seed, epoch, hop,
+the node's id) only, never on the batch around it (include/kgx.h states the
+key derivation, tests/sampling_ref.py restates it in numpy).
+"""
+
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from . import ops as kops
+from .graph import CSRGraph
+from .layers._edges import edge_index_tensor, graph_for
+
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(z: int) -> int:
+    """The generator's mixing step on a Python int (uint64 arithmetic)."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def epoch_seed(seed: int, epoch: int) -> int:
+    """The 64-bit seed of one epoch: splitmix64(splitmix64(seed) + epoch) mod 2^64."""
+    return splitmix64((splitmix64(int(seed) & _M64) + int(epoch)) & _M64)
+
+
+def _ws(nbytes: int, dev: torch.device) -> torch.Tensor:
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+
+
+def _seed_tensor(seeds, dev: torch.device) -> torch.Tensor:
+    if not isinstance(seeds, torch.Tensor):
+        seeds = torch.as_tensor(np.asarray(seeds))
+    if seeds.dim() != 1:
+        raise ValueError(f"seeds must be a 1-d list of node ids, got shape {tuple(seeds.shape)}")
+    return seeds.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def sample_neighbors(g: CSRGraph, seeds: torch.Tensor, fanout: int, seed: int, hop: int = 0):
+    """One hop of fan-out sampling over g's rows (kgx_sample_neighbors).
+
+    Returns (rowptr [n_seeds + 1], src [E_s], eid [E_s]), int32 on g's device:
+    row i lists min(deg(seeds[i]), fanout) in-edges of seeds[i] (all of them for
+    fanout = -1) as global source ids and input edge ids."""
+    dev = nat.require_device(g.rowptr, seeds)
+    if seeds.dtype != torch.int32:
+        raise TypeError("sample_neighbors expects int32 seeds")
+    seeds = seeds.contiguous()
+    n = int(seeds.numel())
+    fanout = int(fanout)
+    i32 = dict(dtype=torch.int32, device=dev)
+    if n == 0 and (fanout >= 1 or fanout == -1):
+        return torch.zeros(1, **i32), torch.empty(0, **i32), torch.empty(0, **i32)
+    # fanout -1: the seeds' total degree, on the device (the call checks it against cap anyway)
+    cap = n * fanout if fanout > 0 else (int(g.deg[seeds.long().clamp(0, max(g.n_dst - 1, 0))].sum()) if g.n_dst else 0)
+    L = nat.lib()
+    rowptr = torch.empty(n + 1, **i32)
+    src = torch.empty(max(cap, 1), **i32)
+    eid = torch.empty(max(cap, 1), **i32)
+    nbytes = ctypes.c_size_t(0)
+    nat.check(L.kgx_sample_workspace_bytes(n, ctypes.byref(nbytes)), "kgx_sample_workspace_bytes")
+    ws = _ws(nbytes.value, dev)
+    info = (ctypes.c_int64 * 4)()
+    nat.check(
+        L.kgx_sample_neighbors(
+            nat.ptr(g.rowptr), nat.ptr(g.col), nat.ptr(g.eid), g.n_dst, nat.ptr(seeds), n, fanout,
+            int(seed) & _M64, int(hop), nat.ptr(rowptr), nat.ptr(src), nat.ptr(eid), max(cap, 0),
+            nat.ptr(ws), nbytes.value, info, nat.stream(dev),
+        ),
+        "kgx_sample_neighbors",
+    )
+    e = int(info[0])
+    return rowptr, src[:e], eid[:e]
+
+
+def relabel_frontier(nodes: torch.Tensor, frontier: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor,
+                     node_map: torch.Tensor):
+    """Local ids of one hop (kgx_relabel_frontier): (new_nodes, src_local,
+    dst_local).  node_map: int32 [n_nodes], all -1 on entry and on return."""
+    dev = nat.require_device(nodes, frontier, rowptr, src, node_map)
+    n_known, n_f, e = int(nodes.numel()), int(frontier.numel()), int(src.numel())
+    n_nodes = int(node_map.numel())
+    i32 = dict(dtype=torch.int32, device=dev)
+    new_nodes = torch.empty(max(e, 1), **i32)
+    src_local = torch.empty(max(e, 1), **i32)
+    dst_local = torch.empty(max(e, 1), **i32)
+    L = nat.lib()
+    nbytes = ctypes.c_size_t(0)
+    nat.check(L.kgx_relabel_workspace_bytes(e, n_nodes, ctypes.byref(nbytes)), "kgx_relabel_workspace_bytes")
+    ws = _ws(nbytes.value, dev)
+    info = (ctypes.c_int64 * 4)()
+    nat.check(
+        L.kgx_relabel_frontier(
+            nat.ptr(nodes), n_known, nat.ptr(frontier), n_f, nat.ptr(rowptr), nat.ptr(src), e,
+            nat.ptr(node_map), n_nodes, nat.ptr(new_nodes), nat.ptr(src_local), nat.ptr(dst_local),
+            nat.ptr(ws), nbytes.value, info, nat.stream(dev),
+        ),
+        "kgx_relabel_frontier",
+    )
+    return new_nodes[: int(info[0])], src_local[:e], dst_local[:e]
+
+
+@dataclass
+class SampledSubgraph:
+    """A sampled mini-batch in local ids.
+
+    node_ids         int32 [n_sub]   global ids; the seeds first, in the order given,
+                                     then every hop's new nodes in ascending global id
+    edge_index       int32 [2, E_s]  local (src, dst), the hops concatenated in hop order
+    edge_ids         int32 [E_s]     input edge id of every sampled edge
+    n_seeds          the first n_seeds local ids are the seeds
+    hop_node_counts  [n_seeds, nodes added by hop 0, nodes added by hop 1, ...]
+    """
+
+    node_ids: torch.Tensor
+    edge_index: torch.Tensor
+    edge_ids: torch.Tensor
+    n_seeds: int
+    hop_node_counts: list = field(default_factory=list)
+
+    def gather(self, x: torch.Tensor) -> torch.Tensor:
+        """x[node_ids] (kgx_gather_rows): the batch's feature rows, local order."""
+        return kops.gather_rows(x, self.node_ids)
+
+
+class NeighborSampler:
+    """Fan-out neighbour sampler over one graph.
+
+    fanouts: neighbours drawn per node and hop (-1: all of them).  The CSR by
+    destination is built once, through the layers' graph cache (no self loops,
+    no GCN norm), and the sampler owns the dense local-id map the relabel step
+    uses (all -1 between calls)."""
+
+    def __init__(self, edge_index, num_nodes: int, fanouts: list[int], seed: int = 0) -> None:
+        fanouts = [int(k) for k in fanouts]
+        if not fanouts or any(k == 0 or k < -1 for k in fanouts):
+            raise ValueError(f"fanouts must be a non-empty list of k >= 1 or -1, got {fanouts}")
+        self.num_nodes = int(num_nodes)
+        self.fanouts = fanouts
+        self.seed = int(seed)
+        self._edge_index = edge_index  # the graph cache is keyed on the caller's object
+        ei = edge_index_tensor(edge_index, None, allow_transpose=True)
+        self.graph = graph_for(edge_index, ei, self.num_nodes, self.num_nodes)
+        self._map = torch.full((max(self.num_nodes, 1),), -1, dtype=torch.int32, device=self.graph.device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.graph.device
+
+    def sample(self, seeds, epoch: int = 0) -> SampledSubgraph:
+        """One mini-batch around `seeds` (distinct node ids).  ValueError for
+        duplicate seeds, IndexError for a seed outside [0, num_nodes)."""
+        dev = self.device
+        nodes = _seed_tensor(seeds, dev)
+        n_seeds = int(nodes.numel())
+        seed64 = epoch_seed(self.seed, epoch)
+        frontier = nodes
+        counts = [n_seeds]
+        srcs, dsts, eids = [], [], []
+        for hop, k in enumerate(self.fanouts):
+            if frontier.numel() == 0:
+                break
+            rowptr, src, eid = sample_neighbors(self.graph, frontier, k, seed64, hop)
+            new, src_l, dst_l = relabel_frontier(nodes, frontier, rowptr, src, self._map[: self.num_nodes])
+            srcs.append(src_l)
+            dsts.append(dst_l)
+            eids.append(eid)
+            counts.append(int(new.numel()))
+            if new.numel():
+                nodes = torch.cat([nodes, new])
+            frontier = new
+        i32 = dict(dtype=torch.int32, device=dev)
+        if srcs:
+            edge_index = torch.stack([torch.cat(srcs), torch.cat(dsts)])
+            edge_ids = torch.cat(eids)
+        else:
+            edge_index, edge_ids = torch.empty((2, 0), **i32), torch.empty(0, **i32)
+        return SampledSubgraph(node_ids=nodes, edge_index=edge_index, edge_ids=edge_ids, n_seeds=n_seeds,
+                               hop_node_counts=counts)
