@@ -679,6 +679,46 @@ int kgx_relabel_frontier(const int32_t* nodes, int64_t n_known, const int32_t* f
                          int32_t* dst_local, void* workspace, size_t workspace_bytes, int64_t* info,
                          kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Sampled blocks: the CSR pair of one bipartite layer graph of a mini-batch
+ * (DGL's "block" / message-flow graph, PyG's trim_to_layer).
+ *
+ * The sampler gives local ids to the seeds first, then hop by hop, and emits
+ * the hops' edges in that order.  With P_h = the number of nodes after hop
+ * h - 1 (P_0 = the seeds): the merged dst array is non-decreasing, the edges
+ * of hops 0..h are a prefix of the edge list, their destinations are < P_h and
+ * their sources < P_{h+1}.  So the edge list is a destination CSR as it
+ * stands (col = src, eid = the edge's position), the graph a layer needs is a
+ * prefix of it, and only rowptr / deg and the transposed CSR are computed.
+ *
+ * kgx_block_csr: src[E], dst[E] device int32, dst non-decreasing, src in
+ * [0, n_src), dst in [0, n_dst) (no wrap of negative ids: these are the
+ * sampler's local ids).
+ *   rowptr[n_dst+1], deg[n_dst]   optional (both NULL to skip): offsets of the
+ *                                 destination rows, by binary search of dst
+ *   t_rowptr[n_src+1], t_deg[n_src]
+ *   t_col[E]                      destination of each edge, source-major
+ *   t_eid[E]                      position of each edge in src / dst, ascending
+ *                                 inside every row: the input-edge order of
+ *                                 graph.transpose, and the edge's forward slot
+ * The transposed side is a stable rocprim radix sort of (src, position) over
+ * ceil_log2(n_src) bits and a binary search of the sorted keys; the work is
+ * O(E + (n_src + n_dst) log E).  Every output is a pure function of the
+ * inputs: atomics only count violations and fold the two maxima.
+ * info[4] (host): max in-degree, max out-degree, edges with dst[e] < dst[e-1],
+ * ids out of range.  Synchronises `stream` once.  Order violations:
+ * KGX_ERR_ARG; ids out of range: KGX_ERR_INDEX (reported first when both
+ * occur); in either case none of the output arrays is written.
+ * Errors before any device call (KGX_ERR_ARG): null pointers, negative sizes,
+ * E >= 2^31, a workspace smaller than kgx_block_workspace_bytes(E, n_src).
+ * E == 0, n_dst == 0, n_src != n_dst and rows of degree 0 are all valid.
+ * ------------------------------------------------------------------------- */
+int kgx_block_workspace_bytes(int64_t E, int64_t n_src, size_t* bytes);
+int kgx_block_csr(const int32_t* src, const int32_t* dst, int64_t E, int64_t n_src, int64_t n_dst,
+                  int32_t* rowptr, int32_t* deg, int32_t* t_rowptr, int32_t* t_deg, int32_t* t_col,
+                  int32_t* t_eid, void* workspace, size_t workspace_bytes, int64_t* info,
+                  kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

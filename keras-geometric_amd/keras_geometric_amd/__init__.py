@@ -6,7 +6,7 @@ behind the C-ABI in include/kgx.h, registered as torch.ops.kgx.*.
 """
 
 from . import _native, graph, ops
-from .graph import CSRGraph, build_csr, clear_cache
+from .graph import Block, CSRGraph, build_csr, clear_cache
 from .layers import (
     AggregatorFactory,
     AttentionPooling,
@@ -20,7 +20,7 @@ from .layers import (
     Set2Set,
     set_random_seed,
 )
-from .sampling import NeighborSampler, SampledSubgraph
+from .sampling import NeighborSampler, SampledBlocks, SampledSubgraph
 from .utils import GraphData, add_self_loops, batch_graphs, compute_gcn_normalization
 
 __version__ = "0.1.0"
@@ -29,6 +29,7 @@ __all__ = [
     "AggregatorFactory",
     "AttentionPooling",
     "BatchGlobalPooling",
+    "Block",
     "CSRGraph",
     "GATv2Conv",
     "GCNConv",
@@ -38,6 +39,7 @@ __all__ = [
     "MessagePassing",
     "NeighborSampler",
     "SAGEConv",
+    "SampledBlocks",
     "SampledSubgraph",
     "Set2Set",
     "add_self_loops",

@@ -162,6 +162,12 @@ _SIGNATURES = {
         _i32p, _i64, _i32p, _i32p, _i32p,
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
     ],
+    "kgx_block_workspace_bytes": [_i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_block_csr": [
+        _i32p, _i32p, _i64, _i64, _i64,
+        _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+    ],
 }
 _RESTYPES = {"kgx_last_error": ctypes.c_char_p}
 

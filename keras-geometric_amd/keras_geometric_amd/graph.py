@@ -84,6 +84,30 @@ class CSRGraph:
         return self.items, self.n_items, self.split, self.n_split, self.n_slots
 
 
+@dataclass
+class Block:
+    """One layer's bipartite graph of a sampled mini-batch
+    (NeighborSampler.sample_blocks): the layer reads n_src rows (local ids
+    [0, n_src)) and writes the first n_dst of them.
+
+    edge_index  int32 [2, E_b]  local (src, dst): a prefix view of the batch's edge list
+    edge_ids    int32 [E_b]     input edge id of every edge
+    graph       the block's CSRGraph: rowptr / col / deg are prefix views of the
+                outermost block's arrays, eid = the edge position, and
+                extras["T"] holds the transposed graph of kgx_block_csr
+    """
+
+    n_src: int
+    n_dst: int
+    edge_index: torch.Tensor
+    edge_ids: torch.Tensor
+    graph: CSRGraph
+
+    @property
+    def shape(self) -> tuple:
+        return tuple(self.edge_index.shape)
+
+
 # ---------------------------------------------------------------------------
 # GCN dinv as the reference evaluates it
 # ---------------------------------------------------------------------------

@@ -5,6 +5,10 @@ out = act(lin_self(x) + lin_neigh(AGG_{j->i} m_j) + b), optional L2 normalize
 (PoolingAggregator, aggregators.py:254-274).  pool_mlp is row-wise, so it is
 applied once per NODE and the kgx kernel gathers its rows (same values as the
 reference's per-edge application).
+
+inputs[1] may also be a sampled bipartite Block (NeighborSampler.sample_blocks;
+no reference counterpart): x then holds the block's n_src source rows and the
+output its first n_dst rows.
 """
 
 from __future__ import annotations
@@ -14,6 +18,7 @@ from typing import Any
 import torch
 
 from .. import ops as kops
+from ..graph import Block
 from ._edges import edge_index_tensor, graph_for
 from .base import Dense, get_activation, get_initializer, serialize_activation, serialize_initializer, \
     to_device_tensor
@@ -108,13 +113,16 @@ class SAGEConv(MessagePassing):
         node_shape = input_shape[0] if isinstance(input_shape, (list, tuple)) and input_shape else None
         return (node_shape[0] if node_shape else None, self.output_dim)
 
-    def aggregate_neighbors(self, x, edge_index, num_nodes, training=None, *, edge_index_obj=None):
-        """sage_conv.py:300-348 as one fused kgx reduction over gathered rows."""
+    def aggregate_neighbors(self, x, edge_index, num_nodes, training=None, *, edge_index_obj=None, graph=None):
+        """sage_conv.py:300-348 as one fused kgx reduction over gathered rows.
+        graph: the CSRGraph of edge_index when the caller has it (a sampled
+        Block's); otherwise it comes from the graph cache."""
         if edge_index.shape[1] == 0:
             feat = self.pool_mlp.units if (self.actual_aggregator == "pooling" and self.pool_mlp) else x.shape[1]
             return torch.zeros((num_nodes, feat), dtype=x.dtype, device=x.device)
-        g = graph_for(edge_index_obj if edge_index_obj is not None else edge_index, edge_index,
-                      x.shape[0], num_nodes, n_features=x.shape[1])
+        g = graph if graph is not None else graph_for(
+            edge_index_obj if edge_index_obj is not None else edge_index, edge_index,
+            x.shape[0], num_nodes, n_features=x.shape[1])
         if training and self.dropout_rate > 0:
             return self._aggregate_dropped(x, edge_index, g)
         if self.actual_aggregator == "pooling":
@@ -145,6 +153,8 @@ class SAGEConv(MessagePassing):
             raise ValueError("SAGEConv expects inputs to be a list/tuple of [node_features, edge_index]")
         x = to_device_tensor(inputs[0], torch.float32)
         edge_index = inputs[1]
+        if isinstance(edge_index, Block):
+            return self._call_block(x, edge_index, training)
         ei = edge_index_tensor(edge_index, x.device, allow_transpose=True)
         num_nodes = x.shape[0]
         out = self._call_fused(x, ei, edge_index, training)
@@ -153,7 +163,22 @@ class SAGEConv(MessagePassing):
         aggregated = self.aggregate_neighbors(x, ei, num_nodes, training=training, edge_index_obj=edge_index)
         return self.update_nodes(x, aggregated)
 
-    def _call_fused(self, x, ei, edge_index_obj, training):
+    def _call_block(self, x, blk, training):
+        """A sampled bipartite Block as the graph: x holds the block's n_src
+        source rows, the output its first n_dst rows,
+        act(x[:n_dst] W_self + AGG_{e: dst = i} m(x[src_e]) W_neigh + b).  The
+        block carries its CSRGraph (and the transposed one the backward pass
+        gathers through), so the graph cache is not consulted."""
+        if x.dim() != 2 or x.shape[0] != blk.n_src:
+            raise ValueError(f"SAGEConv on a Block expects node features of {blk.n_src} rows (the block's n_src), "
+                             f"got shape {tuple(x.shape)}")
+        out = self._call_fused(x, blk.edge_index, None, training, block=blk)
+        if out is not None:
+            return out
+        aggregated = self.aggregate_neighbors(x, blk.edge_index, blk.n_dst, training=training, graph=blk.graph)
+        return self.update_nodes(x[: blk.n_dst], aggregated)
+
+    def _call_fused(self, x, ei, edge_index_obj, training, block=None):
         """Inference with root_weight and a mean / sum / max aggregator: the
         neighbour map fused into the aggregation (sage_conv.py:404-433 in two
         launches): out = b + x W_self (kgx_dense), then kgx_spmm_gemm gathers,
@@ -172,9 +197,12 @@ class SAGEConv(MessagePassing):
         b = self.bias if use_b else None
         if kops._needs_grad(x, W_self, W_neigh, b):
             return None
-        g = graph_for(edge_index_obj, ei, x.shape[0], x.shape[0], n_features=x.shape[1])
+        if block is not None:  # the update reads the destination rows only
+            g, x_dst = block.graph, x[: block.n_dst]
+        else:
+            g, x_dst = graph_for(edge_index_obj, ei, x.shape[0], x.shape[0], n_features=x.shape[1]), x
         relu = self.activation is torch.relu
-        out = kops.dense(x, W_self, b)
+        out = kops.dense(x_dst, W_self, b)
         kops.aggregate_transform(g, x.contiguous(), W_neigh, self.actual_aggregator, out=out, relu=relu)
         if self.activation is not None and not relu:
             out = self.activation(out)

@@ -9,6 +9,15 @@ with autograd, like on any other edge_index:
     sub = sampler.sample(batch_ids, epoch=e)
     out = layer([sub.gather(x), sub.edge_index])[: sub.n_seeds]
 
+A model of several layers takes the same sample as one bipartite Block per
+layer (sample_blocks; kgx_block_csr), so that layer l computes only the rows
+the layers after it read:
+
+    blocks = sampler.sample_blocks(batch_ids, epoch=e)
+    h = blocks.gather(x)
+    for layer, blk in zip(layers, blocks):
+        h = layer([h, blk])              # [blk.n_src, F] -> [blk.n_dst, F_out]
+
 The reference has no sampler (it trains full-batch); the semantics are those of
 PyG's NeighborLoader without replacement: hop 0 expands the seeds, hop h > 0
 expands exactly the nodes hop h - 1 added, every node is expanded at most once.
@@ -27,7 +36,7 @@ import torch
 
 from . import _native as nat
 from . import ops as kops
-from .graph import CSRGraph
+from .graph import Block, CSRGraph, _build_schedule, default_split_len
 from .layers._edges import edge_index_tensor, graph_for
 
 _M64 = (1 << 64) - 1
@@ -145,6 +154,83 @@ class SampledSubgraph:
         return kops.gather_rows(x, self.node_ids)
 
 
+def block_csr(src: torch.Tensor, dst: torch.Tensor, n_src: int, n_dst: int, forward: bool = True):
+    """The CSR pair of a bipartite block whose edges are sorted by destination
+    (kgx_block_csr).  Returns (rowptr [n_dst + 1], deg [n_dst]) -- (None, None)
+    with forward=False --, (t_rowptr [n_src + 1], t_deg [n_src], t_col [E],
+    t_eid [E]) and (max in-degree, max out-degree); all tensors int32.  The
+    forward CSR's col is `src` and its eid the edge position.  ValueError for
+    an unsorted dst, IndexError for an id out of range."""
+    dev = nat.require_device(src, dst)
+    if src.dtype != torch.int32 or dst.dtype != torch.int32:
+        raise TypeError("block_csr expects int32 src / dst")
+    src, dst = src.contiguous(), dst.contiguous()
+    E = int(src.numel())
+    if int(dst.numel()) != E:
+        raise ValueError(f"src/dst length mismatch: {E} vs {dst.numel()}")
+    n_src, n_dst = int(n_src), int(n_dst)
+    i32 = dict(dtype=torch.int32, device=dev)
+    rowptr = torch.empty(n_dst + 1, **i32) if forward else None
+    deg = torch.empty(max(n_dst, 1), **i32) if forward else None
+    t_rowptr = torch.empty(n_src + 1, **i32)
+    t_deg = torch.empty(max(n_src, 1), **i32)
+    t_col = torch.empty(max(E, 1), **i32)
+    t_eid = torch.empty(max(E, 1), **i32)
+    L = nat.lib()
+    nbytes = ctypes.c_size_t(0)
+    nat.check(L.kgx_block_workspace_bytes(E, n_src, ctypes.byref(nbytes)), "kgx_block_workspace_bytes")
+    ws = _ws(nbytes.value, dev)
+    info = (ctypes.c_int64 * 4)()
+    nat.check(
+        L.kgx_block_csr(
+            nat.ptr(src), nat.ptr(dst), E, n_src, n_dst, nat.ptr(rowptr), nat.ptr(deg),
+            nat.ptr(t_rowptr), nat.ptr(t_deg), nat.ptr(t_col), nat.ptr(t_eid),
+            nat.ptr(ws), nbytes.value, info, nat.stream(dev),
+        ),
+        "kgx_block_csr",
+    )
+    fwd = (rowptr, deg[:n_dst]) if forward else (None, None)
+    return fwd, (t_rowptr, t_deg[:n_src], t_col[:E], t_eid[:E]), (int(info[0]), int(info[1]))
+
+
+@dataclass
+class SampledBlocks:
+    """A sampled mini-batch as one Block per layer, outermost first:
+
+        h = blocks.gather(x)
+        for layer, blk in zip(layers, blocks):
+            h = layer([h, blk])          # [blk.n_src, F] -> [blk.n_dst, F_out]
+
+    blocks[l].n_dst == blocks[l + 1].n_src, and the last block writes the seeds.
+    node_ids, n_seeds and hop_node_counts are those of SampledSubgraph."""
+
+    node_ids: torch.Tensor
+    n_seeds: int
+    hop_node_counts: list
+    blocks: list
+
+    def gather(self, x: torch.Tensor) -> torch.Tensor:
+        """x[node_ids] (kgx_gather_rows): the outermost block's source rows."""
+        return kops.gather_rows(x, self.node_ids)
+
+    def __len__(self) -> int:
+        return len(self.blocks)
+
+    def __getitem__(self, i):
+        return self.blocks[i]
+
+    def __iter__(self):
+        return iter(self.blocks)
+
+
+def _block_graph(n_src: int, n_dst: int, col, eid, rowptr, deg, max_deg: int, n_features: int) -> CSRGraph:
+    kept = int(col.numel())
+    g = CSRGraph(n_src=n_src, n_dst=n_dst, n_input_edges=kept, kept=kept, max_degree=max_deg, flags=0,
+                 rowptr=rowptr, col=col, eid=eid, deg=deg)
+    _build_schedule(g, default_split_len(kept, n_features))
+    return g
+
+
 class NeighborSampler:
     """Fan-out neighbour sampler over one graph.
 
@@ -199,3 +285,70 @@ class NeighborSampler:
             edge_index, edge_ids = torch.empty((2, 0), **i32), torch.empty(0, **i32)
         return SampledSubgraph(node_ids=nodes, edge_index=edge_index, edge_ids=edge_ids, n_seeds=n_seeds,
                                hop_node_counts=counts)
+
+    def sample_blocks(self, seeds, epoch: int = 0, n_features: int = 128) -> SampledBlocks:
+        """The sample of `sample(seeds, epoch)` as one bipartite Block per layer.
+
+        Local ids are given to the seeds first, then hop by hop, so with
+        P_h = sum(hop_node_counts[: h + 1]) the edges of hops 0..h are a prefix
+        of the edge list, sorted by destination, with destinations < P_h and
+        sources < P_{h+1}: block l (outermost first) is the prefix of hops
+        0..L-1-l with n_dst = P_{L-1-l}, n_src = P_{L-l}.  A hop that never ran
+        (the frontier emptied) adds no nodes and no edges.  The forward CSR is
+        computed once, for the outermost block; every block gets its own
+        transposed CSR (kgx_block_csr) and its schedules.  n_features sizes the
+        schedules' hub chunks, as in the layers' graph cache."""
+        return self._blocks_of(*self._sample_hops(seeds, epoch), n_features=n_features)
+
+    def _blocks_of(self, nodes, edge_index, edge_ids, counts, e_counts, n_features: int = 128) -> SampledBlocks:
+        """The blocks of one _sample_hops draw (everything after the sample itself)."""
+        L = len(self.fanouts)
+        P = np.cumsum(counts + [0] * (L + 1 - len(counts))).tolist()  # P[h] = nodes before hop h runs
+        Ep = np.cumsum(e_counts + [0] * (L - len(e_counts))).tolist()  # Ep[h] = edges of hops 0..h
+        src, dst = edge_index[0], edge_index[1]
+        pos = torch.arange(Ep[-1], dtype=torch.int32, device=self.device)
+        blocks = []
+        rowptr = deg = None
+        for layer in range(L):
+            h = L - 1 - layer
+            n_dst, n_src, e = P[h], P[h + 1], Ep[h]
+            fwd, (t_rowptr, t_deg, t_col, t_eid), (max_in, max_out) = block_csr(src[:e], dst[:e], n_src, n_dst,
+                                                                               forward=layer == 0)
+            if layer == 0:
+                rowptr, deg = fwd
+            g = _block_graph(n_src, n_dst, src[:e], pos[:e], rowptr[: n_dst + 1], deg[:n_dst], max_in, n_features)
+            t = _block_graph(n_dst, n_src, t_col, t_eid, t_rowptr, t_deg, max_out, n_features)
+            t.extras["fwd_slot"] = t_eid.long()  # as graph.transpose leaves it
+            g.extras["T"] = t
+            blocks.append(Block(n_src=n_src, n_dst=n_dst, edge_index=edge_index[:, :e], edge_ids=edge_ids[:e], graph=g))
+        return SampledBlocks(node_ids=nodes, n_seeds=counts[0], hop_node_counts=counts, blocks=blocks)
+
+    def _sample_hops(self, seeds, epoch: int):
+        """sample()'s draw, with the edge count of every hop that ran:
+        (node_ids, edge_index, edge_ids, hop_node_counts, hop_edge_counts)."""
+        dev = self.device
+        nodes = _seed_tensor(seeds, dev)
+        seed64 = epoch_seed(self.seed, epoch)
+        frontier = nodes
+        counts, e_counts = [int(nodes.numel())], []
+        srcs, dsts, eids = [], [], []
+        for hop, k in enumerate(self.fanouts):
+            if frontier.numel() == 0:
+                break
+            rowptr, src, eid = sample_neighbors(self.graph, frontier, k, seed64, hop)
+            new, src_l, dst_l = relabel_frontier(nodes, frontier, rowptr, src, self._map[: self.num_nodes])
+            srcs.append(src_l)
+            dsts.append(dst_l)
+            eids.append(eid)
+            counts.append(int(new.numel()))
+            e_counts.append(int(eid.numel()))
+            if new.numel():
+                nodes = torch.cat([nodes, new])
+            frontier = new
+        i32 = dict(dtype=torch.int32, device=dev)
+        if srcs:
+            edge_index = torch.stack([torch.cat(srcs), torch.cat(dsts)])
+            edge_ids = torch.cat(eids)
+        else:
+            edge_index, edge_ids = torch.empty((2, 0), **i32), torch.empty(0, **i32)
+        return nodes, edge_index, edge_ids, counts, e_counts
