@@ -258,6 +258,46 @@ int kgx_spmm_ex2(int reduce, int epilogue, const int32_t* rowptr, const int32_t*
                  int64_t ld_x, float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed,
                  float* partials, int32_t* counters, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Fused multi-aggregation: several reducers of one neighbourhood from ONE
+ * gather of every neighbour row (no reference counterpart as a whole; each
+ * block is kgx_spmm's single-reducer arithmetic, aggregators.py:48-232).
+ *   out[row, k*F + f] = REDUCE_{reduces[k]} { table[idx[e], f] : e in CSR row }
+ * reduces: host array of n_red (1..5) distinct kgx_reduce ids; the blocks are
+ *   concatenated along the feature axis in that order (ld_out >= n_red * F),
+ *   the layout a following Dense wants.  No edge weights, dropout or epilogues.
+ * With idx = col it is the node gather; with idx = eid and table = a per-edge
+ *   message tensor [E,F] it reduces arbitrary messages.
+ * Work list, as kgx_spmm: items == NULL is EXACT mode (every row of `rows`
+ *   reduced by one lane group in CSR order: each block bit-identical to
+ *   kgx_spmm's EXACT result, KGX_STD included); otherwise the item list of
+ *   kgx_schedule_build.  Unsplit items are reduced with the EXACT arithmetic;
+ *   a chunk of a split row writes its raw state to `partials` and a fix-up
+ *   kernel folds each row's chunks in chunk order (no atomics: results are
+ *   bit-identical from run to run).  Unlike kgx_spmm, KGX_STD follows the
+ *   schedule too: a chunk keeps M2 = sum (v - chunk_mean)^2 and its length,
+ *   merged pairwise as M2 = M2a + M2b + d^2 na nb / (na + nb), d = mean_b - mean_a
+ *   (a re-association of the two-pass form on split rows only).
+ * partials: per slot one section of F floats for each accumulator the list
+ *   needs, in the order {sum (sum | mean | std), amax (max), amax of -m (min),
+ *   M2 (std)}, then with std 4 floats whose first is the chunk length.
+ *   kgx_multi_aggr_partials_floats gives n_slots times that; partials_floats
+ *   is the buffer's size in floats (chunk stores past it are dropped).
+ * KGX_ERR_ARG (before any device work, nothing written): null reduces / rowptr /
+ *   rows / idx / table / out, n_red outside 1..5, an unknown or repeated id,
+ *   negative sizes, ld_out < n_red*F, ld_table < F or >= 2^31, split rows
+ *   without split list or partials, partials_floats below one slot per split row.
+ * ------------------------------------------------------------------------- */
+int kgx_multi_aggr(int n_red, const int* reduces,
+                   const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                   const int32_t* items, int64_t n_items,
+                   const int32_t* split, int64_t n_split,
+                   const int32_t* idx, const float* table, int64_t ld_table, int64_t F,
+                   float* out, int64_t ld_out,
+                   float* partials, int64_t partials_floats,
+                   kgx_stream_t stream);
+int kgx_multi_aggr_partials_floats(int n_red, const int* reduces, int64_t n_slots, int64_t F, int64_t* floats);
+
 /* Message dropout mask (training; GCNConv.message dropout, gcn_conv.py:237-242;
  * GATv2 attention dropout, gatv2_conv.py:252-253): element (key, f) is kept
  * with probability 1 - p and scaled by 1/(1-p).  The mask is a pure function

@@ -16,6 +16,7 @@ from .layers import (
     GINConv,
     GlobalPooling,
     MessagePassing,
+    PNAConv,
     SAGEConv,
     Set2Set,
     set_random_seed,
@@ -38,6 +39,7 @@ __all__ = [
     "GraphData",
     "MessagePassing",
     "NeighborSampler",
+    "PNAConv",
     "SAGEConv",
     "SampledBlocks",
     "SampledSubgraph",

@@ -83,6 +83,12 @@ _SIGNATURES = {
         _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64,
         _f32p, _f32p, _i64, ctypes.c_float, _i32p, ctypes.c_float, ctypes.c_uint64, _f32p, _i32p, ctypes.c_void_p,
     ],
+    "kgx_multi_aggr": [
+        _int, ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
+        _i32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, ctypes.c_void_p,
+    ],
+    "kgx_multi_aggr_partials_floats": [_int, ctypes.POINTER(ctypes.c_int), _i64, _i64,
+                                       ctypes.POINTER(ctypes.c_int64)],
     "kgx_dropout_mask": [ctypes.c_uint64, ctypes.c_float, _i32p, _i64, _i64, _f32p, ctypes.c_void_p],
     "kgx_spmm_gemm": [
         _int, _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,

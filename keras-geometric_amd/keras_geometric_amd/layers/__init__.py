@@ -6,6 +6,7 @@ from .aggregators import (
     MaxAggregator,
     MeanAggregator,
     MinAggregator,
+    MultiAggregator,
     PoolingAggregator,
     StdAggregator,
     SumAggregator,
@@ -16,6 +17,7 @@ from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
 from .gin_conv import GINConv
 from .message_passing import MessagePassing
+from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
 from .sage_conv import SAGEConv
 
@@ -34,6 +36,8 @@ __all__ = [
     "MeanAggregator",
     "MessagePassing",
     "MinAggregator",
+    "MultiAggregator",
+    "PNAConv",
     "PoolingAggregator",
     "SAGEConv",
     "Sequential",

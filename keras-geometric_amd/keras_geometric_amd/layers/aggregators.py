@@ -130,6 +130,43 @@ class PoolingAggregator(Aggregator):
         return "pooling"
 
 
+class MultiAggregator(Aggregator):
+    """Several registered aggregators of the same messages, concatenated along
+    the feature axis in the order given (no reference counterpart): one fused
+    kgx_multi_aggr pass reads every message once for all of them."""
+
+    def __init__(self, names) -> None:
+        names = [names] if isinstance(names, str) else list(names)
+        if not names:
+            raise ValueError("MultiAggregator needs at least one aggregator name")
+        available = AggregatorFactory.get_available_aggregators()
+        for n in names:
+            if n not in available:
+                raise ValueError(f"Invalid aggregator: {n}. Available aggregators: {available}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"MultiAggregator: repeated aggregator in {names}")
+        self.names = names
+        # the std path's take() out-of-range rule (Aggregator.aggregate) applies when std is among them
+        self.reduce = "std" if "std" in names else names[0]
+
+    def _reduce(self, graph: CSRGraph, messages: torch.Tensor, exact: bool) -> torch.Tensor:
+        return kops.multi_aggregate(graph, messages, self.names, by_edge=True, exact=exact)
+
+    def aggregate(self, messages, target_idx, dim_size: int, *, graph: CSRGraph | None = None,
+                  exact: bool = False) -> torch.Tensor:
+        messages = to_device_tensor(messages, torch.float32)
+        if messages.dim() == 1:
+            messages = messages.unsqueeze(-1)
+        if messages.shape[0] == 0:  # no messages: zeros of the concatenated width
+            return torch.zeros((dim_size, len(self.names) * messages.shape[1]), dtype=messages.dtype,
+                               device=messages.device)
+        return super().aggregate(messages, target_idx, dim_size, graph=graph, exact=exact)
+
+    @property
+    def name(self) -> str:
+        return "+".join(self.names)
+
+
 class AggregatorFactory:
     """Registry (aggregators.py:281-343)."""
 
@@ -147,6 +184,10 @@ class AggregatorFactory:
             available = list(cls._AGGREGATORS.keys())
             raise ValueError(f"Invalid aggregator: {aggregator_name}. Available aggregators: {available}")
         return cls._AGGREGATORS[aggregator_name](**kwargs)
+
+    @classmethod
+    def create_multi(cls, names) -> "MultiAggregator":
+        return MultiAggregator(names)
 
     @classmethod
     def create_pooling(cls, pool_mlp) -> PoolingAggregator:

@@ -24,11 +24,17 @@ from .base import Layer, to_device_tensor
 
 
 class MessagePassing(Layer):
-    def __init__(self, aggregator: str = "mean", exact: bool | None = None, **kwargs) -> None:
+    def __init__(self, aggregator: str | list[str] = "mean", exact: bool | None = None, **kwargs) -> None:
         super().__init__(**kwargs)
-        self.aggregator_name: str = aggregator
-        self._aggregator: Aggregator = AggregatorFactory.create(aggregator)
-        self.aggregator: str = aggregator
+        if isinstance(aggregator, (list, tuple)):
+            # several aggregators of one neighbourhood, concatenated: [N, R * F] (no reference counterpart)
+            self._aggregator: Aggregator = AggregatorFactory.create_multi(aggregator)
+            self.aggregator_name = self._aggregator.name
+            self.aggregator = list(aggregator)
+        else:
+            self.aggregator_name: str = aggregator
+            self._aggregator = AggregatorFactory.create(aggregator)
+            self.aggregator: str = aggregator
         self.supported_aggregators: list[str] = AggregatorFactory.get_available_aggregators()
         # cache of the int32 edge_index (message_passing.py:41-42, 256-268)
         self._cached_edge_idx: torch.Tensor | None = None
@@ -80,10 +86,13 @@ class MessagePassing(Layer):
             return torch.zeros((0, feature_dim), dtype=x_i.dtype, device=x_i.device)
         ei = edge_index_tensor(edge_index, x_i.device, allow_transpose=False)
         if ei.shape[1] == 0:  # :185-188
-            return torch.zeros((n_dst, x_i.shape[1]), dtype=x_i.dtype, device=x_i.device)
+            width = x_i.shape[1] * (len(self.aggregator) if isinstance(self.aggregator, list) else 1)
+            return torch.zeros((n_dst, width), dtype=x_i.dtype, device=x_i.device)
         g = graph_for(edge_index, ei, n_src, n_dst, n_features=x_j.shape[1])
 
-        if edge_attr is None and self._fusable():
+        if edge_attr is None and self._fusable() and isinstance(self.aggregator, list):
+            aggregated = kops.multi_aggregate(g, x_j.contiguous(), self.aggregator, exact=self.exact)
+        elif edge_attr is None and self._fusable():
             aggregated = kops.aggregate(g, x_j.contiguous(), self._aggregator.reduce, exact=self.exact)
         else:
             # generic path: user hooks on per-edge tensors (indices validated by the CSR build)
@@ -129,7 +138,10 @@ class MessagePassing(Layer):
         return super().forward(inputs, *args, **kwargs)
 
     def compute_output_shape(self, input_shape):
-        return input_shape[0] if isinstance(input_shape, (list, tuple)) else input_shape
+        shape = input_shape[0] if isinstance(input_shape, (list, tuple)) else input_shape
+        if isinstance(self.aggregator, list) and shape is not None and len(shape) >= 2 and shape[-1] is not None:
+            return tuple(shape[:-1]) + (shape[-1] * len(self.aggregator),)  # [N, R * F]
+        return shape
 
     def get_config(self) -> dict[str, Any]:
         config = super().get_config()

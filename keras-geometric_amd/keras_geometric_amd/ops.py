@@ -5,6 +5,7 @@ libkgx.so on torch's current HIP stream, with a fake (meta) kernel so that
 torch.compile / symbolic tracing sees shapes without running the GPU.
 
   kgx::spmm   fused gather -> message -> segment {sum,mean,max,min,std} -> epilogue
+  kgx::multi_aggr  several of those reducers from one gather, blocks concatenated
   kgx::gatv2  fused GATv2 attention aggregation
   kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
   kgx::gather_rows, kgx::scatter_f32   row movement helpers
@@ -15,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -863,6 +864,203 @@ def aggregate(
                                   float(dropout), int(seed))
     return _aggregate_raw(g, table, red, weighted, by_edge, epilogue, bias, xroot, gin_scale, exact, float(dropout),
                           int(seed))
+
+
+# ---------------------------------------------------------------------------
+# Fused multi-aggregation (kgx_multi_aggr): several reducers, one gather
+# ---------------------------------------------------------------------------
+def _reduce_list(reduces) -> list[int]:
+    """Reducer names / ids -> 1..5 distinct kgx_reduce ids, in the caller's order."""
+    if isinstance(reduces, (str, int)):
+        reduces = [reduces]
+    ids = []
+    for r in reduces:
+        if isinstance(r, str) and r not in nat.REDUCE_IDS:
+            raise ValueError(f"multi_aggregate: unknown reducer {r!r}; available: {list(nat.REDUCE_IDS)}")
+        ids.append(_reduce_id(r))
+    if not 1 <= len(ids) <= 5 or len(set(ids)) != len(ids) or any(i < nat.SUM or i > nat.STD for i in ids):
+        raise ValueError(f"multi_aggregate: 1..5 distinct reducers of {list(nat.REDUCE_IDS)} expected, got "
+                         f"{list(reduces)}")
+    return ids
+
+
+def _c_ints(ids):
+    return (ctypes.c_int * len(ids))(*ids)
+
+
+def multi_aggr_partials_floats(reduces, n_slots: int, F: int) -> int:
+    """Floats of split-row chunk state kgx_multi_aggr needs (kgx_multi_aggr_partials_floats)."""
+    ids = _reduce_list(reduces)
+    floats = ctypes.c_int64(0)
+    nat.check(nat.lib().kgx_multi_aggr_partials_floats(len(ids), _c_ints(ids), int(n_slots), int(F),
+                                                       ctypes.byref(floats)), "kgx_multi_aggr_partials_floats")
+    return floats.value
+
+
+def multi_aggr_gathers(F: int) -> int:
+    """Neighbour rows kgx_multi_aggr keeps in flight per lane group for a contiguous
+    [*, F] table (multi_aggr.hip's Gathers<NT>::U): also the longest row whose std
+    second pass reuses the gathered registers.  Tests place row degrees around it."""
+    vec = 4 if F % 4 == 0 else (2 if F % 2 == 0 else 1)
+    cv = min(F, 256 * vec) // vec
+    return 6 if cv <= 64 else (4 if cv <= 128 else 2)
+
+
+@torch.library.custom_op("kgx::multi_aggr", mutates_args=())
+def multi_aggr(
+    table: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    idx: torch.Tensor,
+    n_slots: int,
+    reduces: List[int],
+) -> torch.Tensor:
+    """out[:, k*F:(k+1)*F] = reducer reduces[k] of the rows table[idx[e]] of every CSR row."""
+    table = _f32c(table)
+    dev = nat.require_device(table, rowptr, rows, idx, items, split)
+    ids = _reduce_list(list(reduces))
+    n_dst = rowptr.numel() - 1
+    F = table.shape[1]
+    out = torch.empty((n_dst, len(ids) * F), dtype=torch.float32, device=dev)
+    if n_dst == 0 or F == 0:
+        return out
+    if idx.numel() == 0 or table.shape[0] == 0:  # no edges: every block of an empty row is 0
+        return out.zero_()
+    n_items = 0 if items is None else items.shape[0]
+    n_split = 0 if split is None else split.shape[0]
+    partials, floats = None, 0
+    if items is not None and n_split > 0:
+        floats = multi_aggr_partials_floats(ids, n_slots, F)
+        partials = torch.empty(floats, dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_multi_aggr(
+            len(ids), _c_ints(ids), nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items,
+            nat.ptr(split), n_split, nat.ptr(idx), nat.ptr(table), table.stride(0), F,
+            nat.ptr(out), out.stride(0), nat.ptr(partials), floats, nat.stream(dev),
+        ),
+        "kgx_multi_aggr",
+    )
+    return out
+
+
+@multi_aggr.register_fake
+def _multi_aggr_fake(table, rowptr, rows, items, split, idx, n_slots, reduces):
+    return table.new_empty((rowptr.shape[0] - 1, len(reduces) * table.shape[1]))
+
+
+def _multi_aggregate_raw(g, table, ids, by_edge, exact):
+    items, _, split, _, n_slots = g.work(exact)
+    idx = g.eid if by_edge else g.col
+    return _timed(lambda: torch.ops.kgx.multi_aggr(table, g.rowptr, g.rows, items, split, idx, n_slots, ids))
+
+
+def _multi_backward(g: CSRGraph, ids: list[int], by_edge: bool, table: torch.Tensor, full: torch.Tensor,
+                    full_ids: list[int], grad_out: torch.Tensor, exact: bool) -> torch.Tensor:
+    """d loss / d table of multi_aggregate, from existing kernels and the saved
+    forward blocks `full` (mean and std are not recomputed).  With n the clamped
+    fp32 count, A = g_std / (n std) (NaN where n <= 1: _reduce_backward's convention)
+    and D = g_sum + g_mean / n - A * mean:
+        grad_x = T_sum(D) + x * T_sum(A)
+    as ONE transposed kgx_spmm sum over the 2F-wide table [D | A]; max and min
+    add kgx_spmm_max_backward passes into one zeroed buffer.  by_edge: every
+    message receives its row's terms through row_of_slot, std's in the centred
+    form A * (m_e - mean) of _reduce_backward's by-edge branch."""
+    from . import graph as G
+
+    F = table.shape[1]
+    grad_out = grad_out.contiguous()
+
+    def blk(t, id_list, red):
+        k = id_list.index(red)
+        return t[:, k * F:(k + 1) * F]
+
+    count = torch.clamp(g.deg, max=1 << 24).float().unsqueeze(1)
+    n = torch.clamp(count, min=1e-8)
+    D = A = mean = None
+    if nat.SUM in ids:
+        D = blk(grad_out, ids, nat.SUM)
+    if nat.MEAN in ids:
+        d = blk(grad_out, ids, nat.MEAN) / n
+        D = d if D is None else D + d
+    if nat.STD in ids:
+        A = blk(grad_out, ids, nat.STD) / (n * blk(full, full_ids, nat.STD))
+        A = torch.where(count > 1, A, torch.full_like(A, float("nan")))
+        mean = blk(full, full_ids, nat.MEAN)
+        if not by_edge:  # per edge the centred form A * (m_e - mean) is applied instead
+            d = A * mean
+            D = -d if D is None else D - d
+    gt = None
+    if nat.MAX in ids or nat.MIN in ids:
+        table = table.contiguous()
+        gt = torch.zeros_like(table)
+        idx = g.eid if by_edge else g.col
+        for red in (nat.MAX, nat.MIN):
+            if red not in ids:
+                continue
+            go = blk(grad_out, ids, red)
+            nat.check(
+                nat.lib().kgx_spmm_max_backward(
+                    red, 0, nat.ptr(g.rowptr), g.n_dst, nat.ptr(idx), nat.ptr(table), table.stride(0), F,
+                    nat.ptr(go), go.stride(0), nat.ptr(gt), gt.stride(0), nat.stream(table.device),
+                ),
+                "kgx_spmm_max_backward",
+            )
+    if D is None and A is None:
+        return gt
+    if by_edge:  # each message receives its row's terms, as _reduce_backward's by-edge branches
+        rows = G.row_of_slot(g).long()
+        eid = g.eid.long()
+        vals = D.index_select(0, rows) if D is not None else None
+        if A is not None:
+            v = A.index_select(0, rows) * (table.index_select(0, eid) - mean.index_select(0, rows))
+            vals = v if vals is None else vals + v
+        lin = grad_out.new_zeros((table.shape[0], F))
+        lin.index_copy_(0, eid, vals)
+    else:
+        t = G.transpose(g)
+        DA = (torch.cat([D, A], dim=1) if A is not None else D).contiguous()
+        S = _aggregate_raw(t, DA, nat.SUM, False, False, nat.EPI_NONE, None, None, 1.0, exact)
+        lin = S[:, :F] + table * S[:, F:] if A is not None else S
+    return lin if gt is None else gt.add_(lin)
+
+
+class _MultiAggregateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, g, ids, by_edge, exact):
+        # std's gradient reads the row means: keep a mean block beside the requested ones
+        full_ids = ids + [nat.MEAN] if nat.STD in ids and nat.MEAN not in ids else ids
+        full = _multi_aggregate_raw(g, table, full_ids, by_edge, exact)
+        ctx.g, ctx.ids, ctx.full_ids, ctx.by_edge, ctx.exact = g, ids, full_ids, by_edge, exact
+        ctx.save_for_backward(table, full)
+        if full_ids is ids:
+            return full
+        return full[:, : len(ids) * table.shape[1]].contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        table, full = ctx.saved_tensors
+        g_table = None
+        if ctx.needs_input_grad[0]:
+            g_table = _multi_backward(ctx.g, ctx.ids, ctx.by_edge, table, full, ctx.full_ids, grad_out, ctx.exact)
+        return g_table, None, None, None, None
+
+
+def multi_aggregate(g: CSRGraph, table: torch.Tensor, reduces, *, by_edge: bool = False,
+                    exact: bool = False) -> torch.Tensor:
+    """[n_dst, len(reduces) * F]: block k is reducer reduces[k] ("sum", "mean",
+    "max", "min", "std" or their ids, each at most once) of table[idx[e]] over
+    every row's edges, all from ONE gather of each neighbour row (kgx_multi_aggr)
+    instead of one kgx_spmm launch per reducer.  by_edge as in aggregate().
+    exact=True: every block bit-identical to aggregate(..., exact=True).
+    Otherwise the schedule is used, std included: split hub rows fold their
+    chunks' (sum, M2) pairwise in chunk order, deterministic but re-associated.
+    Differentiable in table; the backward is composed from the existing kernels."""
+    ids = _reduce_list(reduces)
+    if _needs_grad(table):
+        return _MultiAggregateFn.apply(table, g, ids, bool(by_edge), bool(exact))
+    return _multi_aggregate_raw(g, table, ids, by_edge, exact)
 
 
 def _tiny_of(g, items):
