@@ -759,6 +759,71 @@ int kgx_block_csr(const int32_t* src, const int32_t* dst, int64_t E, int64_t n_s
                   int32_t* t_eid, void* workspace, size_t workspace_bytes, int64_t* info,
                   kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Link prediction: edge scores from node rows (the SDDMM-shaped counterpart of
+ * kgx_spmm) and the negative sampler that feeds it.  No reference counterpart.
+ *
+ * kgx_edge_dot:
+ *   out[p * ld_out + k] = sum_f xa[a_idx[p], f] * xb[b_idx[p * K + k], f]    p < P, k < K
+ * xa [n_a, ld_a >= F] and xb [n_b, ld_b >= F] are fp32 with unit column stride
+ * and may be the same pointer; a_idx[P] and b_idx[P * K] are int32.  K = 1 is a
+ * plain pair list, K = 1 + Q one positive followed by its Q negatives: the xa
+ * row is loaded once per p, so a positive costs (1 + K) * 4F bytes.
+ *   perm   optional int32[P], a permutation of [0, P): row p is stored at
+ *          out[perm[p] * ld_out + k] (a graph's own edges scored in CSR order
+ *          and returned in input-edge order).  An entry outside [0, P) is
+ *          counted in `bad` and its row is not stored.
+ *   bad    optional device int32, zeroed by the caller, never read back here:
+ *          the number of indices outside their table.  Such an index is clamped
+ *          for the load and its score is stored as NaN; nothing is read out of
+ *          range.
+ * Every score is a function of its two rows and F alone: with V = 4, 2 or 1
+ * the widest of those dividing F and G = min(64, next_pow2(F / V)), lane l of a
+ * group of G lanes adds the products of columns (t * G + l) * V .. + V, t = 0,
+ * 1, ..., in column order into one accumulator (separately rounded multiply and
+ * add, starting from +0), and the G accumulators are folded by the xor
+ * butterfly of distances G/2, ..., 1.  Rows that are not 16 (8) byte aligned
+ * are read with narrower loads in the same lane layout, so alignment, p, k, K,
+ * P, perm and the grid size never change a bit; inf and NaN follow IEEE in
+ * their own pair's score only.  No allocation, no synchronise.
+ * Errors before any device call (KGX_ERR_ARG): null a_idx / b_idx / out (xa /
+ * xb unless F == 0), negative sizes, K < 1, ld_a < F, ld_b < F, ld_out < K, P * K >= 2^31,
+ * an ld >= 2^31, an empty table with P > 0.  P == 0: KGX_OK, nothing launched;
+ * F == 0: every score is +0.
+ *
+ * kgx_negative_edges: Q corrupted sources for each positive (source ->
+ * destination a[p]) over a destination CSR whose rows are sorted ascending
+ * (col_sorted).  One lane per output; all arithmetic uint64 modulo 2^64,
+ * splitmix64 as in kgx_sample_neighbors:
+ *   ks   = splitmix64(seed ^ splitmix64(uint64(uint32(keys[p]))))
+ *   rs   = splitmix64(ks + q)                                q < Q
+ *   try t = 0 .. max_tries-1:  r = splitmix64(rs + t);  cand = ((r >> 32) * n_src) >> 32
+ *   reject cand if (flags & KGX_NEG_NO_SELF) and cand == a[p], or
+ *                  (flags & KGX_NEG_REJECT_EDGES) and cand is in
+ *                  col_sorted[rowptr[a[p]] .. rowptr[a[p] + 1])  (binary search)
+ *   out[p * ld_out + q] = the first candidate not rejected
+ * If every try is rejected the output is the last try's candidate and stats[0]
+ * counts it.  An a[p] outside [0, n_dst) is counted in stats[1] (once per p);
+ * nothing is read for it and its outputs are -1.  stats: device int32[2],
+ * zeroed by the caller; no output value depends on an atomic.  With keys = the
+ * positives' input edge ids a positive draws the same negatives in every
+ * batch, at every position, on every device (tests/negative_ref.py restates it
+ * bit for bit).  ld_out >= Q: `out` may point into column 1 of a [P, 1 + Q]
+ * index array.  No synchronise.
+ * Errors before any device call (KGX_ERR_ARG): null a / keys / out / stats
+ * (rowptr / col_sorted with KGX_NEG_REJECT_EDGES), Q < 1, max_tries outside
+ * 1..64, n_src < 1 or >= 2^31, negative sizes, unknown flags, ld_out < Q,
+ * P * Q >= 2^31.  P == 0: KGX_OK.
+ * ------------------------------------------------------------------------- */
+enum { KGX_NEG_NO_SELF = 1, KGX_NEG_REJECT_EDGES = 2 };
+enum { KGX_EDGE_DOT_U = 8 }; /* candidate rows in flight per group */
+int kgx_edge_dot(const float* xa, int64_t n_a, int64_t ld_a, const float* xb, int64_t n_b, int64_t ld_b,
+                 int64_t F, const int32_t* a_idx, const int32_t* b_idx, int64_t P, int64_t K,
+                 const int32_t* perm, float* out, int64_t ld_out, int32_t* bad, kgx_stream_t stream);
+int kgx_negative_edges(const int32_t* rowptr, const int32_t* col_sorted, int64_t n_dst, int64_t n_src,
+                       const int32_t* a, const int32_t* keys, int64_t P, int Q, uint64_t seed, int max_tries,
+                       int flags, int32_t* out, int64_t ld_out, int32_t* stats, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

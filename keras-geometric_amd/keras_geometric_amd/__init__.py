@@ -11,6 +11,7 @@ from .layers import (
     AggregatorFactory,
     AttentionPooling,
     BatchGlobalPooling,
+    DotProductDecoder,
     GATv2Conv,
     GCNConv,
     GINConv,
@@ -21,7 +22,7 @@ from .layers import (
     Set2Set,
     set_random_seed,
 )
-from .sampling import NeighborSampler, SampledBlocks, SampledSubgraph
+from .sampling import EdgeBatch, NegativeSampler, NeighborSampler, SampledBlocks, SampledSubgraph
 from .utils import GraphData, add_self_loops, batch_graphs, compute_gcn_normalization
 
 __version__ = "0.1.0"
@@ -32,12 +33,15 @@ __all__ = [
     "BatchGlobalPooling",
     "Block",
     "CSRGraph",
+    "DotProductDecoder",
+    "EdgeBatch",
     "GATv2Conv",
     "GCNConv",
     "GINConv",
     "GlobalPooling",
     "GraphData",
     "MessagePassing",
+    "NegativeSampler",
     "NeighborSampler",
     "PNAConv",
     "SAGEConv",

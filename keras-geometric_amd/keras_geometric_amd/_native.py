@@ -27,6 +27,8 @@ DENSE_RELU, DENSE_ACCUMULATE = 1, 2
 DENSE_MAX_K, DENSE_MAX_N = 256, 256
 POOL_SCORE_TANH = 1
 POOL_MAX_F = 256
+NEG_NO_SELF, NEG_REJECT_EDGES = 1, 2
+EDGE_DOT_U = 8
 
 REDUCE_IDS = {"sum": SUM, "mean": MEAN, "max": MAX, "min": MIN, "std": STD}
 
@@ -173,6 +175,14 @@ _SIGNATURES = {
         _i32p, _i32p, _i64, _i64, _i64,
         _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+    ],
+    "kgx_edge_dot": [
+        _f32p, _i64, _i64, _f32p, _i64, _i64, _i64, _i32p, _i32p, _i64, _i64,
+        _i32p, _f32p, _i64, _i32p, ctypes.c_void_p,
+    ],
+    "kgx_negative_edges": [
+        _i32p, _i32p, _i64, _i64, _i32p, _i32p, _i64, _int, ctypes.c_uint64, _int, _int,
+        _i32p, _i64, _i32p, ctypes.c_void_p,
     ],
 }
 _RESTYPES = {"kgx_last_error": ctypes.c_char_p}

@@ -13,6 +13,7 @@ from .aggregators import (
 )
 from .attention_pooling import AttentionPooling, Set2Set
 from .base import Dense, Layer, Sequential, set_random_seed
+from .decoders import DotProductDecoder
 from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
 from .gin_conv import GINConv
@@ -27,6 +28,7 @@ __all__ = [
     "AttentionPooling",
     "BatchGlobalPooling",
     "Dense",
+    "DotProductDecoder",
     "GATv2Conv",
     "GCNConv",
     "GINConv",

@@ -8,6 +8,7 @@ torch.compile / symbolic tracing sees shapes without running the GPU.
   kgx::multi_aggr  several of those reducers from one gather, blocks concatenated
   kgx::gatv2  fused GATv2 attention aggregation
   kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
+  kgx::edge_dot  edge scores from node rows (link prediction)
   kgx::gather_rows, kgx::scatter_f32   row movement helpers
 """
 
@@ -1696,3 +1697,198 @@ def softmax_pool(
         return _SoftmaxPoolFn.apply(x, s, score_u, score_c, g, bool(tanh))
     a = _pool_args(g)
     return _timed(lambda: torch.ops.kgx.softmax_pool(x, *a[:5], s, score_u, score_c, bool(tanh), a[5]))
+
+
+# ---------------------------------------------------------------------------
+# Edge scores for link prediction (kgx_edge_dot): node rows -> edge values
+# ---------------------------------------------------------------------------
+def _row_table(t: torch.Tensor, what: str) -> torch.Tensor:
+    """A [n, F] fp32 table the kernel can read in place: unit column stride and
+    rows that do not overlap (row views with ld > F pass through uncopied)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"kgx kernels compute in fp32; got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError(f"edge_dot: {what} must be [n, F], got {tuple(t.shape)}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+@torch.library.custom_op("kgx::edge_dot", mutates_args=("bad",))
+def edge_dot_op(
+    xa: torch.Tensor,
+    xb: torch.Tensor,
+    a_idx: torch.Tensor,
+    b_idx: torch.Tensor,
+    perm: Optional[torch.Tensor],
+    bad: torch.Tensor,
+) -> torch.Tensor:
+    """out[p, k] = xa[a_idx[p]] . xb[b_idx[p, k]] (row p stored at perm[p] when
+    given); `bad` (int32 [1]) counts the indices outside their table."""
+    xa, xb = _row_table(xa, "xa"), _row_table(xb, "xb")
+    dev = nat.require_device(xa, xb, a_idx, b_idx, perm, bad)
+    if a_idx.dtype != torch.int32 or b_idx.dtype != torch.int32 or b_idx.dim() != 2:
+        raise TypeError("kgx::edge_dot expects int32 a_idx [P] and b_idx [P, K]")
+    if xa.shape[1] != xb.shape[1]:
+        raise ValueError(f"edge_dot: feature widths differ ({xa.shape[1]} vs {xb.shape[1]})")
+    P, K = b_idx.shape
+    if a_idx.numel() != P or (perm is not None and perm.numel() != P):
+        raise ValueError("edge_dot: a_idx, b_idx and perm disagree on P")
+    out = torch.empty((P, K), dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_edge_dot(
+            nat.ptr(xa), xa.shape[0], _ld(xa), nat.ptr(xb), xb.shape[0], _ld(xb), xa.shape[1],
+            nat.ptr(a_idx.contiguous()), nat.ptr(b_idx.contiguous()), P, K,
+            nat.ptr(perm.contiguous()) if perm is not None else None, nat.ptr(out), out.stride(0) if P else K,
+            nat.ptr(bad), nat.stream(dev),
+        ),
+        "kgx_edge_dot",
+    )
+    return out
+
+
+@edge_dot_op.register_fake
+def _edge_dot_fake(xa, xb, a_idx, b_idx, perm, bad):
+    return xa.new_empty((b_idx.shape[0], b_idx.shape[1]))
+
+
+def _weighted_sum(g: CSRGraph, table: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """out[i] = sum_{slot s of row i} w[s] * table[col[s]] (kgx::spmm, per-call weights)."""
+    items, _, split, _, n_slots = g.work(False)
+    return _timed(lambda: torch.ops.kgx.spmm(
+        table, g.rowptr, g.rows, items, split, g.col, w, n_slots, nat.SUM, nat.EPI_NONE, None, None, 1.0,
+        None, 0.0, 0, g.n_long if items is not None else _exact_short(g, nat.SUM),
+    ))
+
+
+def edge_dot_pair_graph(a_idx: torch.Tensor, b_idx: torch.Tensor, n_a: int, n_b: int) -> CSRGraph:
+    """The pair graph of an edge_dot call, for its backward: one row per xa row,
+    one edge (b_idx[p, k] -> a_idx[p]) per score, input edge id p * K + k.  A
+    pair with an index outside its table (a NaN score) is left out -- its
+    destination becomes -1, which kgx_csr_build drops -- so it passes no
+    gradient and a negative source never wraps to another row."""
+    from . import graph as G
+
+    K = b_idx.shape[1]
+    src = b_idx.reshape(-1)
+    dst = a_idx.repeat_interleave(K)
+    bad = (src < 0) | (src >= n_b) | (dst < 0) | (dst >= n_a)
+    return G.build_csr(src.masked_fill(bad, 0).contiguous(), dst.masked_fill(bad, -1).contiguous(), n_b, n_a)
+
+
+class _EdgeDotFn(torch.autograd.Function):
+    """Backward by existing deterministic kernels only: with D = d loss / d out,
+        d xa[i] = sum_{pairs with a = i} D * xb[b]      (weighted kgx::spmm over the pair graph)
+        d xb[j] = sum_{pairs with b = j} D * xa[a]      (the same over its graph.transpose)
+    w = D in each CSR's slot order (eid: the pair's position in `out`).  A table
+    passed as both xa and xb receives both, summed by autograd."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, a_idx, b_idx, perm, bad, graph_of):
+        ctx.graph_of = graph_of
+        ctx.save_for_backward(xa, xb)
+        return torch.ops.kgx.edge_dot(xa, xb, a_idx, b_idx, perm, bad)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        xa, xb = ctx.saved_tensors
+        g = ctx.graph_of()
+        d = grad_out.contiguous().reshape(-1)
+        g_xa = g_xb = None
+        if ctx.needs_input_grad[0]:
+            g_xa = _weighted_sum(g, xb, d.index_select(0, g.eid.long()))
+        if ctx.needs_input_grad[1]:
+            t = G.transpose(g)
+            g_xb = _weighted_sum(t, xa, d.index_select(0, t.eid.long()))
+        return g_xa, g_xb, None, None, None, None, None
+
+
+def _check_bad(bad: torch.Tensor, what: str) -> None:
+    n = int(bad.item())
+    if n:
+        raise IndexError(f"{what}: {n} index(es) outside their table (their scores are NaN)")
+
+
+def edge_dot(xa: torch.Tensor, xb: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, *, check: bool = True,
+             cache: dict | None = None) -> torch.Tensor:
+    """out[p, k] = xa[a_idx[p]] . xb[b_idx[p, k]] -> [P, K] ([P] for a 1-d b_idx).
+
+    xa [n_a, F] and xb [n_b, F] are fp32 tables (row views are read in place)
+    and may be the same tensor; a_idx [P] and b_idx [P, K] are node ids.  K = 1 +
+    Q scores a positive and its Q negatives from one load of the xa row.  A
+    score is a function of its two rows and F alone (bit-identical at every p,
+    k, K and P).  An index outside its table gives a NaN score; check=True reads
+    the kernel's counter back (one synchronise) and raises IndexError, check=
+    False never synchronises.  Differentiable in xa and xb through weighted
+    kgx::spmm sums over the pair graph and its transpose, both deterministic;
+    the pair graph is built only when a gradient is asked for -- a build_csr
+    and a graph.transpose per new index arrays, each with a host read-back, so
+    a backward synchronises even with check=False -- and kept in `cache` (a
+    dict, e.g. EdgeBatch.extras) when one is given, with the index arrays and
+    table heights it was built for: other arrays or heights rebuild it.  A
+    pair with an index outside its table is not in the pair graph and passes
+    no gradient."""
+    dev = nat.require_device(xa, xb, a_idx, b_idx)
+    one_d = b_idx.dim() == 1
+    a_idx = a_idx.to(torch.int32).reshape(-1).contiguous()
+    b2 = (b_idx.unsqueeze(1) if one_d else b_idx).to(torch.int32).contiguous()
+    if b2.dim() != 2 or b2.shape[0] != a_idx.numel() or b2.shape[1] < 1:
+        raise ValueError(f"edge_dot: b_idx {tuple(b_idx.shape)} does not match a_idx {tuple(a_idx.shape)}")
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if _needs_grad(xa, xb):
+        n_a, n_b = xa.shape[0], xb.shape[0]
+
+        # the cached graph belongs to these index arrays (kept alive beside it, so their
+        # addresses cannot be handed out again) at these versions and table heights
+        key = (n_a, n_b, a_idx.data_ptr(), tuple(a_idx.shape), a_idx._version,
+               b2.data_ptr(), tuple(b2.shape), b2._version)
+
+        def graph_of():
+            hit = cache.get("pair_graph_key") if cache is not None else None
+            if hit is not None and hit[0] == key and cache.get("pair_graph") is not None:
+                return cache["pair_graph"]
+            g = edge_dot_pair_graph(a_idx, b2, n_a, n_b)
+            if cache is not None:
+                cache["pair_graph"] = g
+                cache["pair_graph_key"] = (key, a_idx, b2)
+            return g
+
+        out = _EdgeDotFn.apply(xa, xb, a_idx, b2, None, bad, graph_of)
+    else:
+        out = _timed(lambda: torch.ops.kgx.edge_dot(xa, xb, a_idx, b2, None, bad))
+    if check:
+        _check_bad(bad, "edge_dot")
+    return out.reshape(-1) if one_d else out
+
+
+def edge_dot_graph(g: CSRGraph, x_dst: torch.Tensor, x_src: torch.Tensor, *, check: bool = True) -> torch.Tensor:
+    """Scores of the CSR's own edges, in input-edge order: out[e] = x_dst[dst_e] .
+    x_src[src_e] -> [E].  The kernel walks the edges in CSR order (a_idx =
+    row_of_slot(g), b_idx = g.col) and stores through perm = g.eid; the
+    backward reuses g and its cached transpose.  A graph built with self loops
+    is rejected (its extra slots are not input edges)."""
+    from . import graph as G
+
+    if g.flags & nat.CSR_SELF_LOOPS:
+        raise ValueError("edge_dot_graph: the graph was built with self loops; score a graph of the input edges")
+    if g.kept != g.n_input_edges:
+        raise ValueError(f"edge_dot_graph: the CSR holds {g.kept} of {g.n_input_edges} input edges")
+    if x_dst.dim() != 2 or x_src.dim() != 2 or x_dst.shape[0] != g.n_dst or x_src.shape[0] != g.n_src:
+        raise ValueError(f"edge_dot_graph: expected x_dst [{g.n_dst}, F] and x_src [{g.n_src}, F], got "
+                         f"{tuple(x_dst.shape)} and {tuple(x_src.shape)}")
+    dev = nat.require_device(x_dst, x_src, g.rowptr)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    args = (x_dst, x_src, G.row_of_slot(g), g.col.reshape(-1, 1), g.eid, bad)
+    if _needs_grad(x_dst, x_src):
+        out = _EdgeDotFn.apply(*args, lambda: g)
+    else:
+        out = _timed(lambda: torch.ops.kgx.edge_dot(*args))
+    if check:
+        _check_bad(bad, "edge_dot_graph")
+    return out.reshape(-1)

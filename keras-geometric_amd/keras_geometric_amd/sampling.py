@@ -24,6 +24,14 @@ expands exactly the nodes hop h - 1 added, every node is expanded at most once.
 The sample is counter based: a node's neighbours depend on (seed, epoch, hop,
 the node's id) only, never on the batch around it (include/kgx.h states the
 key derivation, tests/sampling_ref.py restates it in numpy).
+
+For link prediction, `NegativeSampler` turns a batch of positive edges into an
+`EdgeBatch` with Q corrupted sources each (kgx_negative_edges), keyed the same
+way on the positive's input edge id (tests/negative_ref.py):
+
+    neg = NegativeSampler(edge_index, num_nodes, num_negatives=4, seed=0)
+    batch = neg.sample(edge_ids, epoch=e)         # a_idx [P], b_idx [P, 1 + Q], labels
+    scores = DotProductDecoder()([z, batch])      # [P, 1 + Q], column 0 the positive
 """
 
 from __future__ import annotations
@@ -352,3 +360,151 @@ class NeighborSampler:
         else:
             edge_index, edge_ids = torch.empty((2, 0), **i32), torch.empty(0, **i32)
         return nodes, edge_index, edge_ids, counts, e_counts
+
+
+# ---------------------------------------------------------------------------
+# Link prediction: positives with their negatives
+# ---------------------------------------------------------------------------
+def negative_edges(rowptr: torch.Tensor | None, col_sorted: torch.Tensor | None, n_dst: int, n_src: int,
+                   a: torch.Tensor, keys: torch.Tensor, num_negatives: int, seed: int, *, max_tries: int = 8,
+                   no_self: bool = True, reject_edges: bool = True, out: torch.Tensor | None = None,
+                   stats: torch.Tensor | None = None):
+    """Q corrupted sources for every positive (kgx_negative_edges): (out, stats).
+
+    a [P]: the positives' destinations, keys [P]: their keys (input edge ids),
+    both int32; rowptr / col_sorted: a destination CSR whose rows are sorted
+    ascending.  out: int32 [P, >= Q] with unit column stride (a column slice of
+    a wider index array is written in place), made [P, Q] when None.  stats:
+    int32 [2] on the device, zeroed here when None: outputs that used up
+    max_tries, and positives whose destination is outside [0, n_dst) (their
+    outputs are -1).  Never synchronises."""
+    dev = nat.require_device(a, keys, rowptr, col_sorted, out, stats)
+    if a.dtype != torch.int32 or keys.dtype != torch.int32:
+        raise TypeError("negative_edges expects int32 a / keys")
+    a, keys = a.contiguous(), keys.contiguous()
+    P, Q = int(a.numel()), int(num_negatives)
+    if int(keys.numel()) != P:
+        raise ValueError(f"a / keys length mismatch: {P} vs {keys.numel()}")
+    if out is None:
+        out = torch.empty((P, max(Q, 0)), dtype=torch.int32, device=dev)
+    if out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != P or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError("negative_edges: out must be an int32 [P, >= Q] array with unit column stride")
+    if stats is None:
+        stats = torch.zeros(2, dtype=torch.int32, device=dev)
+    flags = (nat.NEG_NO_SELF if no_self else 0) | (nat.NEG_REJECT_EDGES if reject_edges else 0)
+    ld_out = out.stride(0) if P > 1 else max(out.shape[1], Q)
+    nat.check(
+        nat.lib().kgx_negative_edges(
+            nat.ptr(rowptr), nat.ptr(col_sorted), int(n_dst), int(n_src), nat.ptr(a), nat.ptr(keys), P, Q,
+            int(seed) & _M64, int(max_tries), flags, nat.ptr(out), ld_out, nat.ptr(stats), nat.stream(dev),
+        ),
+        "kgx_negative_edges",
+    )
+    return out, stats
+
+
+@dataclass
+class EdgeBatch:
+    """A batch of positive edges with their negatives (NegativeSampler.sample).
+
+    a_idx     int32 [P]         the positives' destinations (global ids)
+    b_idx     int32 [P, 1 + Q]  column 0 the true source, columns 1.. the Q corrupted sources
+    labels    fp32  [P, 1 + Q]  1 in column 0, 0 elsewhere
+    edge_ids  int32 [P]         the positives' input edge ids (the sampler's keys)
+    stats     int32 [2] on the device: negatives that used up max_tries, edge ids out of range
+    extras    per-batch cache (ops.edge_dot keeps the backward's pair graph here)
+    """
+
+    a_idx: torch.Tensor
+    b_idx: torch.Tensor
+    labels: torch.Tensor
+    edge_ids: torch.Tensor
+    stats: torch.Tensor
+    extras: dict = field(default_factory=dict)
+
+    @property
+    def num_negatives(self) -> int:
+        return int(self.b_idx.shape[1]) - 1
+
+    def fallbacks(self) -> int:
+        """Negatives whose every try was rejected (they hold the last candidate).
+        Reads the device counters: the batch's only synchronise.  IndexError
+        for an edge id outside the sampler's edge list."""
+        fell, bad = (int(v) for v in self.stats.tolist())
+        if bad:
+            raise IndexError(f"EdgeBatch: {bad} edge id(s) outside the sampler's edge list")
+        return fell
+
+    def relabel(self):
+        """(node_ids, a_local, b_local): the batch's distinct node ids,
+        ascending (the seeds to hand to NeighborSampler), and a_idx / b_idx as
+        positions in node_ids -- the indices into the encoder's seed rows.  A
+        composed torch.unique: it runs once per batch, beside the encoder's
+        own sampling."""
+        P = int(self.a_idx.numel())
+        ids, inv = torch.unique(torch.cat([self.a_idx, self.b_idx.reshape(-1)]), sorted=True, return_inverse=True)
+        inv = inv.to(torch.int32)
+        return ids, inv[:P].contiguous(), inv[P:].reshape(self.b_idx.shape).contiguous()
+
+
+class NegativeSampler:
+    """Positive edges with Q uniformly drawn corrupted sources each, on the device.
+
+    A negative of the positive (s -> d) is a pair (s' -> d): s' uniform over
+    the nodes, redrawn (at most max_tries times) while it is d itself
+    (no_self) or a source of one of d's input edges (reject_edges).  The
+    draw is keyed on (seed, epoch, the positive's input edge id, q) only
+    (kgx_negative_edges; the epoch enters as in epoch_seed), so a positive
+    draws the same negatives in every batch, at every position, on every
+    device.  The CSR by destination is built once, through the layers' graph
+    cache; its rows are sorted ascending once, here, with one composed
+    torch.sort of row * num_nodes + col keys -- per graph, not per batch."""
+
+    def __init__(self, edge_index, num_nodes: int, num_negatives: int, seed: int = 0, reject_edges: bool = True,
+                 no_self: bool = True, max_tries: int = 8) -> None:
+        self.num_nodes = int(num_nodes)
+        self.num_negatives = int(num_negatives)
+        if self.num_nodes < 1 or self.num_negatives < 1:
+            raise ValueError("NegativeSampler needs num_nodes >= 1 and num_negatives >= 1")
+        if not 1 <= int(max_tries) <= 64:
+            raise ValueError(f"max_tries must lie in 1..64, got {max_tries}")
+        self.seed = int(seed)
+        self.reject_edges, self.no_self, self.max_tries = bool(reject_edges), bool(no_self), int(max_tries)
+        self._edge_index = edge_index  # the graph cache is keyed on the caller's object
+        ei = edge_index_tensor(edge_index, None, allow_transpose=True)
+        self.src, self.dst = ei[0].contiguous(), ei[1].contiguous()
+        g = self.graph = graph_for(edge_index, ei, self.num_nodes, self.num_nodes)
+        if g.kept:
+            from .graph import row_of_slot
+
+            keys = row_of_slot(g).long() * self.num_nodes + g.col.long()
+            self.col_sorted = (torch.sort(keys).values % self.num_nodes).to(torch.int32)
+        else:
+            self.col_sorted = torch.zeros(1, dtype=torch.int32, device=g.device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.graph.device
+
+    def sample(self, edge_ids, epoch: int = 0) -> EdgeBatch:
+        """The positives `edge_ids` (input edge ids) with their negatives.  No
+        synchronise: an id outside the edge list gets a_idx = -1 and all-(-1)
+        b_idx (edge_dot scores them NaN) and is reported by fallbacks()."""
+        dev = self.device
+        ids = _seed_tensor(edge_ids, dev)
+        P, Q, E = int(ids.numel()), self.num_negatives, int(self.src.numel())
+        b_idx = torch.empty((P, 1 + Q), dtype=torch.int32, device=dev)
+        if E:
+            ok = (ids >= 0) & (ids < E)
+            safe = ids.clamp(0, E - 1).long()
+            a_idx = torch.where(ok, self.dst[safe], -1)
+            b_idx[:, 0] = torch.where(ok, self.src[safe], -1)
+        else:
+            a_idx = torch.full((P,), -1, dtype=torch.int32, device=dev)
+            b_idx[:, 0] = -1
+        _, stats = negative_edges(self.graph.rowptr, self.col_sorted, self.num_nodes, self.num_nodes, a_idx, ids, Q,
+                                  epoch_seed(self.seed, epoch), max_tries=self.max_tries, no_self=self.no_self,
+                                  reject_edges=self.reject_edges, out=b_idx[:, 1:])
+        labels = torch.zeros((P, 1 + Q), dtype=torch.float32, device=dev)
+        labels[:, 0] = 1.0
+        return EdgeBatch(a_idx=a_idx, b_idx=b_idx, labels=labels, edge_ids=ids, stats=stats)
