@@ -396,6 +396,73 @@ int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_t* rows, in
                       const float* W, int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
                       int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg, kgx_stream_t stream);
 
+/* Sliced schedule of the fused launch (kgx_spmm_gemm_ex4): rows of degree >= T
+ * (the split hub rows among them; T <= split_len) have their edges regrouped by
+ * SOURCE CLASS, a hash of the source id into [0, C): kgx_slice_class below.
+ * Each XCD's L2 then holds one class of the hot source rows instead of a copy
+ * of all of them.  Built once per reused graph, beside the schedule:
+ *   kgx_slice_count: info[0] = rows of degree >= T, info[1] = their edges,
+ *     info[2] = their items (a prefix of the degree-descending item list; only
+ *     items [0, n_long_items) are looked at).  ws: 32 bytes.  Syncs once.
+ *   kgx_slice_build, for rows[0, n_rows_s) (that prefix of the schedule's row
+ *     order) with n_edges_s edges and items [0, n_items_s):
+ *       col_s / w_s [n_edges_s]  the rows' edges, row by row in schedule order,
+ *                                each row grouped by class, CSR order kept
+ *                                inside a class (stable sort; w NULL: no w_s)
+ *       items_s [cap_items][4]   C item lists back to back.  List c: the class-c
+ *                                chunks {row, beg, end, slot} (offsets into
+ *                                col_s, <= split_len edges, slot >= 0), rows in
+ *                                schedule order, then its share of items
+ *                                [n_items_s, n_long_items) of the item list,
+ *                                copied in 16-item tiles dealt round-robin
+ *       lists [C][4]             {first item, items, chunk items, 0} of list c
+ *       fix [n_rows_s][4]        {row, first slot, slots, degree}; a row's slots
+ *                                are consecutive, in class then chunk order
+ *     cap_items >= n_edges_s / split_len + n_rows_s * C + n_long_items - n_items_s.
+ *     info[0] = items in all lists, info[1] = slots, info[2] = items of the
+ *     longest list, info[3] = chunk items.  Deterministic.  Syncs once.
+ * kgx_slice_class: the class of source id `col` (host, pure).
+ * kgx_slice_grid: the grid of a sliced launch, a multiple of n_classes within
+ *   resident_blocks, at most list_tiles blocks per list; 0 = run unsliced. */
+int kgx_slice_class(int32_t col, int n_classes);
+int kgx_slice_grid(int64_t resident_blocks, int64_t list_tiles, int n_classes);
+int kgx_slice_count(const int32_t* rowptr, int64_t n_dst, const int32_t* items, int64_t n_long_items, int32_t T,
+                    void* ws, int64_t* info, kgx_stream_t stream);
+int kgx_slice_workspace_bytes(int64_t n_rows_s, int64_t n_edges_s, int n_classes, size_t* bytes);
+int kgx_slice_build(const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rows,
+                    int64_t n_rows_s, int64_t n_edges_s, const int32_t* items, int64_t n_items_s,
+                    int64_t n_long_items, int32_t split_len, int n_classes, int32_t* col_s, float* w_s,
+                    int32_t* items_s, int64_t cap_items, int32_t* lists, int32_t* fix, void* workspace,
+                    size_t workspace_bytes, int64_t* info, kgx_stream_t stream);
+
+/* kgx_spmm_gemm_ex4: kgx_spmm_gemm_ex3 with a sliced schedule (kgx_slice_build)
+ * for the main kernel: n_classes lists (4 or 8), block b of the main kernel on
+ * list b % n_classes -- an XCD affinity label only: every item is reduced once
+ * by a statically determined block, and results do not depend on where blocks
+ * run.  sl_tiles = ceil(longest list / 16).  The sliced rows' chunks write
+ * partials (n_slots of kgx_slice_build * 128 floats; `partials` must hold the
+ * larger of the two schedules' slots) and sl_split / sl_n_split (the `fix`
+ * records) replace split / n_split; n_long_items is the kgx_slice_build
+ * call's.  head_short_end (<= n_short_end; anything <= n_long_items: none):
+ * under KGX_FUSED_CU_SPLIT the short-row items [n_long_items, head_short_end)
+ * run on the head's CUs behind the main kernel, by the short-row kernel, and
+ * the tail's CUs take the rest -- the knob that rebalances the two legs once
+ * slicing has shortened the head.  Unweighted or weighted sums, one
+ * table, F_in 128, F_out % 16 == 0.  When no multiple of n_classes blocks fits
+ * the launch, it runs unsliced from items / split as kgx_spmm_gemm_ex3 does.
+ * n_classes 0: kgx_spmm_gemm_ex3.  Rows that are not sliced get bit-identical
+ * results either way. */
+int kgx_spmm_gemm_ex4(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                      const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
+                      const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
+                      const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
+                      const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
+                      const float* W, int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
+                      int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
+                      const int32_t* sl_items, const int32_t* sl_lists, int n_classes, int64_t sl_tiles,
+                      const int32_t* sl_idx, const float* sl_w, const int32_t* sl_split, int64_t sl_n_split,
+                      int64_t head_short_end, kgx_stream_t stream);
+
 /* kgx_spmm_gemm_f256: kgx_spmm_gemm for 256-wide rows (F_in == 256, F_out a
  * multiple of 16 <= 256; partials n_slots * 256 floats).  GINConv's
  * (1+eps) x + aggr -> Dense at BASELINE config C4 (gin_conv.py:216-225,

@@ -962,3 +962,304 @@ extern "C" int kgx_tiny_pack(const int32_t* items, int64_t start, int64_t n, con
   out[1] = int64_t(h[1]);
   return KGX_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Sliced schedule of the fused launch (kgx_slice_build, kgx.h): the edges of the
+// rows of degree >= T regrouped by source class, C item lists for the main
+// kernel, one fix-up record per sliced row.  Everything is placed by sorts,
+// scans and binary searches (no atomic scatter), so two builds give the same
+// arrays.
+// ---------------------------------------------------------------------------
+namespace kgx {
+
+// class of a source id: the top bits of a multiplicative hash, scaled to [0, C)
+// (not col % C: ids of user graphs are not scrambled)
+__host__ __device__ __forceinline__ int slice_class(int32_t col, int C) {
+  const uint32_t h = uint32_t(col) * 0x9E3779B1u;
+  return int((uint64_t(h) * uint32_t(C)) >> 32);
+}
+
+// items of the rest list (n_rem items dealt in 16-item tiles round-robin over C lists) that land in list c
+__host__ __device__ __forceinline__ int64_t slice_rest_count(int64_t n_rem, int C, int c) {
+  const int64_t tiles = (n_rem + 15) / 16;
+  if (tiles <= c) return 0;
+  const int64_t mine = (tiles - 1 - c) / C + 1;
+  const bool last_mine = (tiles - 1) % C == c;
+  return mine * 16 - (last_mine ? tiles * 16 - n_rem : 0);
+}
+
+namespace {
+
+__global__ void slice_count_kernel(const int32_t* __restrict__ rowptr, int64_t n_dst, const int4* __restrict__ items,
+                                   int64_t n_long, int32_t T, unsigned long long* __restrict__ st) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  unsigned long long nr = 0, ne = 0, ni = 0;
+  for (int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < n_dst; r += stride) {
+    const int32_t d = rowptr[r + 1] - rowptr[r];
+    if (d >= T) {
+      ++nr;
+      ne += (unsigned long long)d;
+    }
+  }
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n_long; i += stride) {
+    const int4 v = items[i];
+    if (v.w >= 0 || v.z - v.y >= T) ++ni;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    nr += __shfl_xor(nr, o, 64);
+    ne += __shfl_xor(ne, o, 64);
+    ni += __shfl_xor(ni, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {  // integer sums: any order gives the same totals
+    if (nr) atomicAdd(&st[0], nr);
+    if (ne) atomicAdd(&st[1], ne);
+    if (ni) atomicAdd(&st[2], ni);
+  }
+}
+
+__global__ void slice_deg_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rows, int64_t n_s,
+                                 int32_t* __restrict__ deg) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; r <= n_s; r += stride)
+    deg[r] = r < n_s ? rowptr[rows[r] + 1] - rowptr[rows[r]] : 0;
+}
+
+// sliced edge p (row rank r = the last r with eoff[r] <= p): key r * C + class, value = its CSR position
+__global__ void slice_keys_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                  const int32_t* __restrict__ rows, const int32_t* __restrict__ eoff, int64_t n_s,
+                                  int64_t n_e, int C, uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; p < n_e; p += stride) {
+    int64_t lo = 0, hi = n_s;  // eoff[lo] <= p < eoff[hi]  (eoff[n_s] = n_e)
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (int64_t(eoff[mid]) <= p) lo = mid; else hi = mid;
+    }
+    const int32_t e = rowptr[rows[lo]] + int32_t(p - eoff[lo]);
+    keys[p] = uint32_t(lo) * uint32_t(C) + uint32_t(slice_class(col[e], C));
+    vals[p] = e;
+  }
+}
+
+__global__ void slice_gather_kernel(const int32_t* __restrict__ col, const float* __restrict__ w,
+                                    const int32_t* __restrict__ pos, int64_t n_e, int32_t* __restrict__ col_s,
+                                    float* __restrict__ w_s) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; p < n_e; p += stride) {
+    const int32_t e = pos[p];
+    col_s[p] = col[e];
+    if (w_s) w_s[p] = w[e];
+  }
+}
+
+// start[k] = first sorted position with key >= k, k in [0, n_k]; nch / nchT = chunks of group k
+// (rank-major and class-major), one spare zero entry at the end of each so the scans end in the totals
+__global__ void slice_groups_kernel(const uint32_t* __restrict__ keys, int64_t n_e, int64_t n_s, int C,
+                                    int32_t split_len, int32_t* __restrict__ start, int32_t* __restrict__ nch,
+                                    int32_t* __restrict__ nchT) {
+  const int64_t n_k = n_s * C;
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  auto lower = [&](int64_t k) {
+    int64_t lo = 0, hi = n_e;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (int64_t(keys[mid]) < k) lo = mid + 1; else hi = mid;
+    }
+    return int32_t(lo);
+  };
+  for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k <= n_k; k += stride) {
+    const int32_t b = lower(k);
+    start[k] = b;
+    if (k < n_k) {
+      const int32_t len = lower(k + 1) - b;
+      const int32_t nc = (len + split_len - 1) / split_len;
+      nch[k] = nc;
+      nchT[(k % C) * n_s + k / C] = nc;
+    } else {
+      nch[k] = 0;
+      nchT[k] = 0;
+    }
+  }
+}
+
+__global__ void slice_emit_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ deg,
+                                  const int32_t* __restrict__ start, const int32_t* __restrict__ nch,
+                                  const int32_t* __restrict__ soff, const int32_t* __restrict__ toff, int64_t n_s,
+                                  int C, int32_t split_len, int64_t n_rem, int4* __restrict__ items_s,
+                                  int4* __restrict__ lists, int4* __restrict__ fix) {
+  const int64_t n_k = n_s * C;
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < n_k; k += stride) {
+    const int64_t r = k / C;
+    const int c = int(k % C);
+    int64_t rest_before = 0;
+    for (int cc = 0; cc < c; ++cc) rest_before += slice_rest_count(n_rem, C, cc);
+    const int64_t cbase = toff[int64_t(c) * n_s];                   // chunks of the classes before c
+    const int64_t pos = cbase + rest_before + (toff[int64_t(c) * n_s + r] - cbase);  // list base + place in the list
+    const int32_t row = rows[r];
+    const int32_t b0 = start[k], e0 = start[k + 1];
+    for (int32_t j = 0; j < nch[k]; ++j) {
+      const int32_t b = b0 + j * split_len;
+      items_s[pos + j] = make_int4(row, b, min(e0, b + split_len), soff[k] + j);
+    }
+    if (c == 0) fix[r] = make_int4(row, soff[k], soff[k + C] - soff[k], deg[r]);
+    if (r == 0) {
+      const int64_t chunks = toff[int64_t(c + 1) * n_s] - cbase;
+      lists[c] = make_int4(int32_t(cbase + rest_before), int32_t(chunks + slice_rest_count(n_rem, C, c)),
+                           int32_t(chunks), 0);
+    }
+  }
+}
+
+// the other long items, 16-item tiles dealt round-robin behind the lists' chunks
+__global__ void slice_rest_kernel(const int4* __restrict__ items, int64_t n_rem, int C,
+                                  const int4* __restrict__ lists, int4* __restrict__ items_s) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n_rem; j += stride) {
+    const int64_t t = j / 16;
+    const int4 L = lists[t % C];
+    items_s[int64_t(L.x) + L.z + (t / C) * 16 + j % 16] = items[j];
+  }
+}
+
+struct SliceLayout {
+  int32_t *deg, *eoff, *vals, *vals_sorted, *start, *nch, *nchT, *soff, *toff;
+  uint32_t *keys, *keys_sorted;
+  void* tmp;
+  size_t tmp_bytes, total;
+};
+
+SliceLayout slice_layout(void* ws, int64_t n_s, int64_t n_e, int C) {
+  Carve c(ws, ~size_t(0));
+  SliceLayout L;
+  const int64_t n_k = n_s * C + 1;
+  L.deg = c.take<int32_t>(n_s + 1);
+  L.eoff = c.take<int32_t>(n_s + 1);
+  L.keys = c.take<uint32_t>(n_e);
+  L.keys_sorted = c.take<uint32_t>(n_e);
+  L.vals = c.take<int32_t>(n_e);
+  L.vals_sorted = c.take<int32_t>(n_e);
+  L.start = c.take<int32_t>(n_k);
+  L.nch = c.take<int32_t>(n_k);
+  L.nchT = c.take<int32_t>(n_k);
+  L.soff = c.take<int32_t>(n_k);
+  L.toff = c.take<int32_t>(n_k);
+  const size_t sb = sort_temp_bytes(n_e, 32);
+  size_t scb = 0;
+  const int32_t* si = nullptr;
+  int32_t* so = nullptr;
+  (void)rocprim::exclusive_scan(nullptr, scb, si, so, 0, (size_t)n_k, rocprim::plus<int32_t>(), 0, false);
+  L.tmp_bytes = sb > scb ? sb : scb;
+  L.tmp = c.take<char>(L.tmp_bytes);
+  L.total = c.used();
+  return L;
+}
+
+}  // namespace
+}  // namespace kgx
+
+extern "C" int kgx_slice_class(int32_t col, int n_classes) {
+  return n_classes > 0 ? slice_class(col, n_classes) : 0;
+}
+
+extern "C" int kgx_slice_count(const int32_t* rowptr, int64_t n_dst, const int32_t* items, int64_t n_long_items,
+                               int32_t T, void* ws, int64_t* info, kgx_stream_t stream_) {
+  KGX_REQUIRE(rowptr && n_dst >= 0 && n_long_items >= 0 && (items || n_long_items == 0) && T >= 1 && ws && info,
+              KGX_ERR_ARG, "kgx_slice_count: bad arguments");
+  hipStream_t s = as_stream(stream_);
+  auto* st = static_cast<unsigned long long*>(ws);
+  KGX_CHECK_HIP(hipMemsetAsync(st, 0, 4 * sizeof(unsigned long long), s));
+  const int64_t n = n_dst > n_long_items ? n_dst : n_long_items;
+  if (n > 0) {
+    hipLaunchKernelGGL(slice_count_kernel, dim3(grid_for(n, 2048)), dim3(kBlock), 0, s, rowptr, n_dst,
+                       reinterpret_cast<const int4*>(items), n_long_items, T, st);
+    KGX_CHECK_LAUNCH();
+  }
+  unsigned long long h[4];
+  KGX_CHECK_HIP(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+  KGX_CHECK_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < 3; ++k) info[k] = int64_t(h[k]);
+  return KGX_OK;
+}
+
+extern "C" int kgx_slice_workspace_bytes(int64_t n_rows_s, int64_t n_edges_s, int n_classes, size_t* bytes) {
+  KGX_REQUIRE(bytes && n_rows_s >= 0 && n_edges_s >= 0 && n_classes > 0, KGX_ERR_ARG,
+              "kgx_slice_workspace_bytes: bad arguments");
+  *bytes = slice_layout(nullptr, n_rows_s, n_edges_s, n_classes).total;
+  return KGX_OK;
+}
+
+extern "C" int kgx_slice_build(const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rows,
+                               int64_t n_rows_s, int64_t n_edges_s, const int32_t* items, int64_t n_items_s,
+                               int64_t n_long_items, int32_t split_len, int n_classes, int32_t* col_s, float* w_s,
+                               int32_t* items_s, int64_t cap_items, int32_t* lists, int32_t* fix, void* workspace,
+                               size_t workspace_bytes, int64_t* info, kgx_stream_t stream_) {
+  hipStream_t s = as_stream(stream_);
+  const int C = n_classes;
+  KGX_REQUIRE(rowptr && col && rows && items && col_s && items_s && lists && fix && info && (!w == !w_s), KGX_ERR_ARG,
+              "kgx_slice_build: null pointer (w and w_s go together)");
+  KGX_REQUIRE((C == 4 || C == 8) && split_len > 0, KGX_ERR_ARG,
+              "kgx_slice_build: 4 or 8 classes and a positive split_len (got %d, %d)", C, split_len);
+  KGX_REQUIRE(n_rows_s > 0 && n_edges_s >= n_rows_s && n_edges_s < (int64_t(1) << 31) &&
+                  n_rows_s * C < (int64_t(1) << 31) && n_items_s >= 0 && n_items_s <= n_long_items,
+              KGX_ERR_ARG, "kgx_slice_build: sizes out of range");
+  const int64_t n_rem = n_long_items - n_items_s;
+  KGX_REQUIRE(cap_items >= n_edges_s / split_len + n_rows_s * C + n_rem && cap_items < (int64_t(1) << 31), KGX_ERR_ARG,
+              "kgx_slice_build: cap_items %lld too small", (long long)cap_items);
+  SliceLayout L = slice_layout(workspace, n_rows_s, n_edges_s, C);
+  KGX_REQUIRE(workspace && workspace_bytes >= L.total, KGX_ERR_ARG, "kgx_slice_build: workspace %zu < %zu bytes",
+              workspace_bytes, L.total);
+  const int64_t n_k = n_rows_s * C;
+  hipLaunchKernelGGL(slice_deg_kernel, dim3(grid_for(n_rows_s + 1)), dim3(kBlock), 0, s, rowptr, rows, n_rows_s, L.deg);
+  KGX_CHECK_LAUNCH();
+  size_t tb = L.tmp_bytes;
+  KGX_CHECK_HIP(rocprim::exclusive_scan(L.tmp, tb, (const int32_t*)L.deg, L.eoff, 0, (size_t)(n_rows_s + 1),
+                                        rocprim::plus<int32_t>(), s, false));
+  // the caller's edge count must be the rows' (the keys kernel indexes by it)
+  int32_t total = 0;
+  KGX_CHECK_HIP(hipMemcpyAsync(&total, L.eoff + n_rows_s, sizeof(total), hipMemcpyDeviceToHost, s));
+  KGX_CHECK_HIP(hipStreamSynchronize(s));
+  KGX_REQUIRE(int64_t(total) == n_edges_s, KGX_ERR_ARG,
+              "kgx_slice_build: rows[0, %lld) have %d edges, not %lld", (long long)n_rows_s, total,
+              (long long)n_edges_s);
+  hipLaunchKernelGGL(slice_keys_kernel, dim3(grid_for(n_edges_s, 8192)), dim3(kBlock), 0, s, rowptr, col, rows, L.eoff,
+                     n_rows_s, n_edges_s, C, L.keys, L.vals);
+  KGX_CHECK_LAUNCH();
+  tb = L.tmp_bytes;
+  KGX_CHECK_HIP(rocprim::radix_sort_pairs(L.tmp, tb, L.keys, L.keys_sorted, L.vals, L.vals_sorted,
+                                          (unsigned)n_edges_s, 0, ceil_log2_u64(uint64_t(n_k)) + 1, s, false));
+  hipLaunchKernelGGL(slice_gather_kernel, dim3(grid_for(n_edges_s, 8192)), dim3(kBlock), 0, s, col, w, L.vals_sorted,
+                     n_edges_s, col_s, w_s);
+  KGX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(slice_groups_kernel, dim3(grid_for(n_k + 1, 8192)), dim3(kBlock), 0, s, L.keys_sorted, n_edges_s,
+                     n_rows_s, C, split_len, L.start, L.nch, L.nchT);
+  KGX_CHECK_LAUNCH();
+  tb = L.tmp_bytes;
+  KGX_CHECK_HIP(rocprim::exclusive_scan(L.tmp, tb, (const int32_t*)L.nch, L.soff, 0, (size_t)(n_k + 1),
+                                        rocprim::plus<int32_t>(), s, false));
+  tb = L.tmp_bytes;
+  KGX_CHECK_HIP(rocprim::exclusive_scan(L.tmp, tb, (const int32_t*)L.nchT, L.toff, 0, (size_t)(n_k + 1),
+                                        rocprim::plus<int32_t>(), s, false));
+  hipLaunchKernelGGL(slice_emit_kernel, dim3(grid_for(n_k, 8192)), dim3(kBlock), 0, s, rows, L.deg, L.start, L.nch,
+                     L.soff, L.toff, n_rows_s, C, split_len, n_rem, reinterpret_cast<int4*>(items_s),
+                     reinterpret_cast<int4*>(lists), reinterpret_cast<int4*>(fix));
+  KGX_CHECK_LAUNCH();
+  if (n_rem > 0) {
+    hipLaunchKernelGGL(slice_rest_kernel, dim3(grid_for(n_rem, 8192)), dim3(kBlock), 0, s,
+                       reinterpret_cast<const int4*>(items) + n_items_s, n_rem, C,
+                       reinterpret_cast<const int4*>(lists), reinterpret_cast<int4*>(items_s));
+    KGX_CHECK_LAUNCH();
+  }
+  int32_t hl[8][4], slots = 0;
+  KGX_CHECK_HIP(hipMemcpyAsync(hl, lists, size_t(C) * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  KGX_CHECK_HIP(hipMemcpyAsync(&slots, L.soff + n_k, sizeof(slots), hipMemcpyDeviceToHost, s));
+  KGX_CHECK_HIP(hipStreamSynchronize(s));
+  info[0] = info[2] = info[3] = 0;
+  for (int c = 0; c < C; ++c) {
+    info[0] += hl[c][1];
+    info[2] = hl[c][1] > info[2] ? hl[c][1] : info[2];
+    info[3] += hl[c][2];
+  }
+  info[1] = slots;
+  return KGX_OK;
+}

@@ -100,6 +100,17 @@ inline int64_t shared_cap(int64_t full) {
   return c > 0 ? c : 1;
 }
 
+// Grid of a sliced fused launch (kgx_spmm_gemm_ex4): n_classes item lists, block b
+// on list b % n_classes, so the grid is a multiple of n_classes -- the largest
+// one within `resident` blocks, no more than list_tiles blocks per list.  0: no
+// such grid (fewer resident blocks than lists); the launch then runs unsliced.
+inline int64_t slice_grid(int64_t resident, int64_t list_tiles, int n_classes) {
+  if (n_classes <= 0 || list_tiles <= 0) return 0;
+  int64_t per = resident / n_classes;
+  if (per > list_tiles) per = list_tiles;
+  return per > 0 ? per * n_classes : 0;
+}
+
 // A per-host-thread side stream and fork / join events, one set per
 // translation unit (each .hip file's launches fork onto its own stream).
 // Thread-local: concurrent launches from several host threads (one rank per

@@ -23,8 +23,11 @@
 // the gathers (NS: 11.37 ms with f32 MFMA, 10.43 with the split; 10.3 with no
 // MFMA at all).  The next tile's first U rows are prefetched before the MFMA
 // phase; barriers are LDS-only so those gathers stay in flight.  Hub-row
-// chunks write raw partials; the fix-up kernel combines them and applies W in
-// f32 on the VALU.
+// chunks write raw partials; the fix-up kernel combines them in slot order and
+// applies W with the same split product.  With a sliced schedule
+// (kgx_spmm_gemm_ex4) the rows above a degree threshold are cut by SOURCE CLASS
+// instead and block b walks list b % C, so each XCD's L2 keeps one class of the
+// hot source rows (an affinity: results never depend on where a block runs).
 #include <cstdlib>
 #include <type_traits>
 
@@ -88,6 +91,22 @@ struct FusedArgs {
   const float* x2b;
   int32_t n_x1;
   bool cu_split;  // KGX_FUSED_CU_SPLIT (host side only)
+  // sliced schedule (kgx_spmm_gemm_ex4, kgx_slice_build): C complete item lists for the
+  // main kernel, list c = the class-c chunks of the sliced rows (offsets into sl_idx /
+  // sl_w, slot >= 0), then its share of the other long items (offsets into idx / w).
+  // split / n_split are then the sliced rows' fix-up records.  sl_classes = 0: unsliced.
+  const int4* sl_items;
+  const int4* sl_lists;  // [C] {first item, items, chunk items (a prefix of the list), 0}
+  const int32_t* sl_idx;
+  const float* sl_w;
+  int sl_classes;
+  // host side only: 16-item tiles of the longest list, what the sliced launch puts in
+  // place of split / n_split (the unsliced fall-back keeps those), and the end of the
+  // short-row items a CU-split sliced launch runs on the head's CUs
+  int64_t sl_tiles;
+  int64_t sl_head_short_end;
+  const int4* sl_split;
+  int64_t sl_n_split;
 };
 
 // ---- three-way bf16 split of f32 operands (the "bf16x3" product) ---------
@@ -182,7 +201,11 @@ __device__ __forceinline__ const float* gsrc_or_zero(const FusedArgs& a, bool pr
 }
 
 // NARROW: F_in < 128 or F_out not a multiple of 16 (masks compiled in only there)
-template <int RED, bool WEIGHTED, bool TWO, bool NARROW>
+// SLICED: block b walks list b % C of the sliced schedule with index b / C and
+// stride gridDim.x / C (gridDim.x a multiple of C); b % C is an XCD affinity
+// label only -- every item is reduced once by a statically determined block,
+// wherever that block runs.
+template <int RED, bool WEIGHTED, bool TWO, bool NARROW, bool SLICED = false>
 __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedArgs a) {  // TWO: hold 4 waves per SIMD
   using R = RowRed<RED>;
   // gathers in flight per group: at F_in 128 (GCN, NS) 4 beat 6 and 8 with PF = U
@@ -215,8 +238,26 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
   const int c4 = wave * 16 + 4 * q;
   if (tid < kFin) sbias[tid] = (a.bias && tid < a.F_out) ? a.bias[tid] : 0.0f;  // first read after the tile barrier
 
-  const int64_t n_work = a.items ? a.n_long : a.n_rows;
-  const int64_t stride = int64_t(gridDim.x) * kGroups;
+  int64_t n_work = a.items ? a.n_long : a.n_rows;
+  int64_t stride = int64_t(gridDim.x) * kGroups;
+  int64_t first = int64_t(blockIdx.x) * kGroups;
+  const int4* items = a.items;
+  [[maybe_unused]] int64_t n_part = 0;  // the list's leading chunk items: tiles of partials only skip the transform
+  if constexpr (SLICED) {
+    const int cls = int(blockIdx.x) % a.sl_classes;
+    const int4 L = a.sl_lists[cls];
+    items = a.sl_items + L.x;
+    n_work = L.y;
+    n_part = L.z;
+    first = int64_t(int(blockIdx.x) / a.sl_classes) * kGroups;
+    stride = int64_t(int(gridDim.x) / a.sl_classes) * kGroups;
+    if (n_work == 0) return;  // block-uniform, before any barrier: an empty list
+  }
+  // index / weight arrays of the current item (SLICED: a chunk reads the sliced copies)
+  [[maybe_unused]] const int32_t* ip = a.idx;
+  [[maybe_unused]] const float* wp = a.w;
+  auto idx_of = [&](int32_t ee) { return SLICED ? ip[ee] : a.idx[ee]; };
+  auto w_of = [&](int32_t ee) { return SLICED ? wp[ee] : a.w[ee]; };
 
   // software pipeline: the next item's descriptor and its first PF neighbour rows
   // are loaded before the MFMA phase of the current tile, so the gathers are in
@@ -229,12 +270,16 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
     // never under an exec mask; past-the-end groups get an empty item
     const bool live = it < n_work;
     const int64_t itc = live ? it : n_work - 1;
-    if (a.items) {
-      const int4 v = a.items[itc];
+    if (SLICED || a.items) {
+      const int4 v = items[itc];
       row = live ? v.x : -1;
       beg = live ? v.y : 0;
       end = live ? v.z : 0;
       slot = live ? v.w : -1;
+      if constexpr (SLICED) {
+        ip = slot >= 0 ? a.sl_idx : a.idx;
+        if constexpr (WEIGHTED) wp = slot >= 0 ? a.sl_w : a.w;
+      }
     } else {
       const int32_t rw = a.rows[itc];
       const int32_t b0 = a.rowptr[rw], b1 = a.rowptr[rw + 1];
@@ -251,15 +296,15 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int32_t ee = pn > 0 ? beg + (u < pn ? u : pn - 1) : 0;
-      c[u] = a.idx[ee];
-      if constexpr (WEIGHTED) pw[u] = a.w[ee];
+      c[u] = idx_of(ee);
+      if constexpr (WEIGHTED) pw[u] = w_of(ee);
     }
 #pragma unroll
     for (int u = 0; u < PF; ++u) vload<4>(pv[u], gsrc_or_zero<TWO>(a, u < pn, c[u], fg));
   };
 
-  fetch(int64_t(blockIdx.x) * kGroups + g);
-  for (int64_t base = int64_t(blockIdx.x) * kGroups; base < n_work; base += stride) {
+  fetch(first + g);
+  for (int64_t base = first; base < n_work; base += stride) {
     float acc[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] = R::init();
@@ -278,8 +323,8 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
 #pragma unroll
       for (int u = 0; u < B; ++u) {
         const int32_t ee = u < n ? e + u : end - 1;
-        c[u] = a.idx[ee];
-        if constexpr (WEIGHTED) wt[u] = a.w[ee];
+        c[u] = idx_of(ee);
+        if constexpr (WEIGHTED) wt[u] = w_of(ee);
       }
       float v[B][4];
 #pragma unroll
@@ -312,7 +357,9 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
 #pragma unroll
       for (int k = 0; k < 4; ++k) r[k] = f_ok ? r[k] : 0.0f;
     }
-    {
+    // block-uniform: a tile of partial chunks only has no row to transform
+    const bool transform = !SLICED || base + kGroups > n_part;
+    if (transform) {
       bf16x4_t ph, pm, pl;
       split_row128(r, ph, pm, pl);
       *reinterpret_cast<bf16x4_t*>(&tile3[0][g][f]) = ph;
@@ -324,7 +371,7 @@ __global__ __launch_bounds__(kThreads, TWO ? 4 : 1) void spmm_gemm_kernel(FusedA
 
     fetch(base + stride + g);  // next tile's first gathers fly during the MFMAs
 
-    if (mfma_wave) {
+    if (mfma_wave && transform) {
       const int m = wl & 15;
       f32x4_t d0 = {0.0f, 0.0f, 0.0f, 0.0f};
       f32x4_t d1 = {0.0f, 0.0f, 0.0f, 0.0f};  // two accumulation chains
@@ -727,55 +774,94 @@ __global__ __launch_bounds__(kTinyThreads, 1) void spmm_gemm_tiny_kernel(FusedAr
   }
 }
 
-// Split rows: combine chunk partials in order, finish, then out = v @ W + b (VALU).
+// Split rows (hub rows cut into consecutive chunks; with a sliced schedule every
+// row cut by source class): a tile is 16 fix-up records {row, first slot, slots,
+// degree}, one per row group.  Each group combines its row's partials in slot
+// order (8 loads in flight), finishes the row like the main kernel (pre_gin,
+// agg_out) and writes it into the bf16 planes; the eight MFMA waves then apply
+// W in the tiny-row kernel's kstep_t order and store with bias, accumulate and
+// relu.  (The transform used to run on the VALU, 128 x 128 FMAs per row: fine
+// for a few thousand hub rows, not for 10^5 sliced ones.)
 template <int RED, bool NARROW>
-__global__ __launch_bounds__(256) void spmm_gemm_fixup_kernel(FusedArgs a) {
+__global__ __launch_bounds__(kThreads) void spmm_gemm_fixup_kernel(FusedArgs a) {
   using R = RowRed<RED>;
-  __shared__ float vrow[8][kFin];
-  const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
-  for (int64_t base = int64_t(blockIdx.x) * 8; base < a.n_split; base += int64_t(gridDim.x) * 8) {
+  __shared__ __attribute__((aligned(16))) short tile3[kFPlanes][kGroups][kFin + 8];
+  __shared__ __attribute__((aligned(16))) float sbias[kFin];
+  __shared__ int32_t tile_row[kGroups];
+  const int tid = threadIdx.x;
+  const int g = tid >> 5, lane = tid & 31, f = lane * 4;
+  const bool f_ok = !NARROW || f < a.F_in;
+  const int fg = f_ok ? f : 0;
+  const int wave = tid >> 6, wl = tid & 63;
+  const int m = wl & 15, q = wl >> 4;
+  const int n_col = wave * 16 + m;
+  const bool mfma_wave = wave * 16 < a.F_out;
+  const bool w_ok = mfma_wave && (!NARROW || n_col < a.F_out);
+  bf16x8_t wfh[4], wfm[4], wfl[4];
+  load_w128<NARROW>(a, w_ok, n_col, q, wfh, wfm, wfl);
+  const int c4 = wave * 16 + 4 * q;
+  if (tid < kFin) sbias[tid] = (a.bias && tid < a.F_out) ? a.bias[tid] : 0.0f;  // first read after the tile barrier
+
+  for (int64_t base = int64_t(blockIdx.x) * kGroups; base < a.n_split; base += int64_t(gridDim.x) * kGroups) {
     const int64_t it = base + g;
-    int32_t row = -1;
-    if (it < a.n_split) {
-      const int4 s = a.split[it];
-      row = s.x;
-      float acc[4];
+    const bool live = it < a.n_split;
+    const int4 s = a.split[live ? it : a.n_split - 1];  // clamped (n_split >= 1 in a launched kernel)
+    const int32_t row = live ? s.x : -1;
+    const int32_t ns = live ? s.z : 0;
+    float acc[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) acc[k] = R::init();
-      constexpr int B = 8;  // chunk loads in flight, then the in-order combine
-      for (int32_t c0 = 0; c0 < s.z; c0 += B) {
-        float p[B][4];
+    for (int k = 0; k < 4; ++k) acc[k] = R::init();
+    constexpr int B = 8;  // partial loads in flight, then the in-order combine
+    for (int32_t c0 = 0; c0 < ns; c0 += B) {
+      float p[B][4];
 #pragma unroll
-        for (int u = 0; u < B; ++u) vload<4>(p[u], a.partials + int64_t(s.y + (c0 + u < s.z ? c0 + u : s.z - 1)) * kFin + lane * 4);
+      for (int u = 0; u < B; ++u)
+        vload<4>(p[u], a.partials + int64_t(s.y + (c0 + u < ns ? c0 + u : ns - 1)) * kFin + f);
 #pragma unroll
-        for (int u = 0; u < B; ++u)
+      for (int u = 0; u < B; ++u)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc[k] = c0 + u < s.z ? R::combine(acc[k], p[u][k]) : acc[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[k] = R::finish(acc[k], s.w);
-      if (a.pre_gin) {
-        float xv[4];
-        vload<4>(xv, a.x + int64_t(row) * a.ld_x + (!NARROW || lane * 4 < a.F_in ? lane * 4 : 0));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(__fmul_rn(a.gin_scale, xv[k]), acc[k]);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) vrow[g][lane * 4 + k] = acc[k];
-      if (a.agg_out && (!NARROW || lane * 4 < a.F_in)) vstore<4>(a.agg_out + int64_t(row) * a.ld_agg + lane * 4, acc);
+        for (int k = 0; k < 4; ++k) acc[k] = c0 + u < ns ? R::combine(acc[k], p[u][k]) : acc[k];
     }
-    __syncthreads();
-    if (row >= 0) {
-      for (int c = lane; c < a.F_out; c += 32) {
-        float s = 0.0f;
-        for (int k = 0; k < (NARROW ? a.F_in : kFin); ++k) s = fmaf(vrow[g][k], a.W[int64_t(k) * a.F_out + c], s);
-        float v = s + (a.bias ? a.bias[c] : 0.0f);
-        if (a.accumulate) v = __fadd_rn(a.out[int64_t(row) * a.ld_o + c], v);
-        if (a.relu) v = fmaxf(v, 0.0f);
-        a.out[int64_t(row) * a.ld_o + c] = v;
+    float r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = live ? R::finish(acc[k], s.w) : 0.0f;
+    if (live && a.pre_gin) {
+      float xv[4];
+      vload<4>(xv, a.x + int64_t(row) * a.ld_x + fg);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = __fadd_rn(__fmul_rn(a.gin_scale, xv[k]), r[k]);
+    }
+    if (live && a.agg_out && f_ok) vstore<4>(a.agg_out + int64_t(row) * a.ld_agg + f, r);
+    if (NARROW && a.F_in < kFin) {  // wave-uniform: lanes past F_in put zeros in the planes
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = f_ok ? r[k] : 0.0f;
+    }
+    {
+      bf16x4_t ph, pm, pl;
+      split_row128(r, ph, pm, pl);
+      *reinterpret_cast<bf16x4_t*>(&tile3[0][g][f]) = ph;
+      *reinterpret_cast<bf16x4_t*>(&tile3[1][g][f]) = pm;
+      *reinterpret_cast<bf16x4_t*>(&tile3[2][g][f]) = pl;
+    }
+    if (lane == 0) tile_row[g] = row;
+    lds_barrier();
+    if (mfma_wave) {
+      f32x4_t d = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        const bf16x8_t ah = *reinterpret_cast<const bf16x8_t*>(&tile3[0][m][32 * q + 8 * s4]);
+        const bf16x8_t am = *reinterpret_cast<const bf16x8_t*>(&tile3[1][m][32 * q + 8 * s4]);
+        const bf16x8_t al = *reinterpret_cast<const bf16x8_t*>(&tile3[2][m][32 * q + 8 * s4]);
+        d = kstep_t(wfh[s4], wfm[s4], wfl[s4], ah, am, al, d);
+      }
+      const int rr = tile_row[m];
+      if (rr >= 0 && (!NARROW || c4 < a.F_out)) {
+        float4* dst = reinterpret_cast<float4*>(a.out + int64_t(rr) * a.ld_o + c4);
+        const float4 b4 = *reinterpret_cast<const float4*>(&sbias[c4]);
+        store_out4(dst, make_float4(d[0] + b4.x, d[1] + b4.y, d[2] + b4.z, d[3] + b4.w), a.accumulate, a.relu);
       }
     }
-    __syncthreads();
+    lds_barrier();  // every wave is done with the planes and tile_row before the next tile's are written
   }
 }
 
@@ -834,7 +920,8 @@ int launch_tiny(const FusedArgs& a, hipStream_t s, int cus) {
 }
 
 template <int RED, bool W, bool TWO = false, bool NARROW = false>
-int launch(const FusedArgs& a, hipStream_t s) {
+int launch(const FusedArgs& a_in, hipStream_t s) {
+  FusedArgs a = a_in;
   const int64_t work = a.items ? a.n_long : a.n_rows;
   const bool has_short = a.items && a.n_long < a.n_short_end;
   const bool has_tiny = a.tpack && a.n_tiny > 0;
@@ -856,19 +943,49 @@ int launch(const FusedArgs& a, hipStream_t s) {
   // (both named here: the code object keeps its order of kernels, main, fix-up, short, tiny)
   auto k = spmm_gemm_kernel<RED, W, TWO, NARROW>;
   auto fk = spmm_gemm_fixup_kernel<RED, NARROW>;
-  if (work > 0) {
+  bool sliced = false;
+  if constexpr (RED == KGX_SUM && !TWO && !NARROW) {  // the reductions the sliced schedule is enabled for
+    if (a.sl_classes > 0 && work > 0) {
+      auto ks = spmm_gemm_kernel<RED, W, false, false, true>;
+      const int64_t full = occupancy_blocks(ks, kThreads, 2, cus_h);
+      const int64_t grid = slice_grid(a.share_gpu ? shared_cap(full) : full, a.sl_tiles, a.sl_classes);
+      if (grid > 0) {  // (0: no multiple of C fits this launch -- the unsliced launch below)
+        a.split = a.sl_split;
+        a.n_split = a.sl_n_split;
+        hipLaunchKernelGGL(ks, dim3(unsigned(grid)), dim3(kThreads), 0, sh, a);
+        KGX_CHECK_LAUNCH();
+        sliced = true;
+      }
+    }
+  }
+  if (work > 0 && !sliced) {
     const int64_t need = (work + kGroups - 1) / kGroups;
     hipLaunchKernelGGL(k, dim3(fused_grid(a, need, occupancy_blocks(k, kThreads, 2, cus_h))), dim3(kThreads), 0, sh, a);
     KGX_CHECK_LAUNCH();
   }
-  if (has_short && launch_short<RED, W, TWO, NARROW>(a, st, cus_t) != KGX_OK) return KGX_ERR_HIP;
+  // Rebalance of a CU-split sliced launch: the head leg got shorter, so the first short-row
+  // items [n_long, hs_end) run on the head's CUs, by the same short-row kernel (same bits),
+  // behind the main kernel and the fix-up; the tail leg takes the rest.
+  int64_t hs_end = a.n_long;
+  if (sliced && cus_h > 0 && a.sl_head_short_end > a.n_long)
+    hs_end = a.sl_head_short_end < a.n_short_end ? a.sl_head_short_end : a.n_short_end;
+  if (has_short && hs_end < a.n_short_end) {
+    FusedArgs t = a;
+    t.n_long = hs_end;
+    if (launch_short<RED, W, TWO, NARROW>(t, st, cus_t) != KGX_OK) return KGX_ERR_HIP;
+  }
   if (has_tiny && launch_tiny<RED, W, TWO, NARROW>(a, st, cus_t) != KGX_OK) return KGX_ERR_HIP;
   if (a.items && a.n_split > 0) {
     // the hub fix-up reads only the main kernel's partials and writes only split rows: behind
     // the main kernel on its stream -- split, on the head's CUs, hidden behind the longer tail leg
-    const int64_t blocks = (a.n_split + 7) / 8;
-    hipLaunchKernelGGL(fk, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(256), 0, sh, a);
+    const int64_t blocks = (a.n_split + kGroups - 1) / kGroups;
+    hipLaunchKernelGGL(fk, dim3(fused_grid(a, blocks, occupancy_blocks(fk, kThreads, 2, cus_h))), dim3(kThreads), 0, sh, a);
     KGX_CHECK_LAUNCH();
+  }
+  if (hs_end > a.n_long) {
+    FusedArgs h = a;
+    h.n_short_end = hs_end;
+    if (launch_short<RED, W, TWO, NARROW>(h, sh, cus_h) != KGX_OK) return KGX_ERR_HIP;
   }
   KGX_CHECK_HIP(join.join());
   return KGX_OK;
@@ -921,7 +1038,35 @@ extern "C" int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_
                                  const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
                                  float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
                                  kgx_stream_t stream_) {
+  return kgx_spmm_gemm_ex4(reduce, rowptr, rows, n_rows, items, n_items, n_long_items, n_short_end, tiny_pack, tiny_w,
+                           n_tiny_deg2, split, n_split, idx, w, x, ld_x, x2, n_x1, F_in, W, F_out, bias, flags,
+                           gin_scale, out, ld_out, partials, agg_out, ld_agg, nullptr, nullptr, 0, 0, nullptr, nullptr,
+                           nullptr, 0, -1, stream_);
+}
+
+extern "C" int kgx_slice_grid(int64_t resident_blocks, int64_t list_tiles, int n_classes) {
+  return int(slice_grid(resident_blocks, list_tiles, n_classes));
+}
+
+extern "C" int kgx_spmm_gemm_ex4(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                                 const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
+                                 const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
+                                 const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
+                                 const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
+                                 const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
+                                 float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
+                                 const int32_t* sl_items, const int32_t* sl_lists, int n_classes, int64_t sl_tiles,
+                                 const int32_t* sl_idx, const float* sl_w, const int32_t* sl_split,
+                                 int64_t sl_n_split, int64_t head_short_end, kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
+  KGX_REQUIRE(n_classes == 0 || ((n_classes == 4 || n_classes == 8) && items && sl_items && sl_lists && sl_idx &&
+                                 sl_split && sl_n_split > 0 && sl_tiles > 0 && partials && (!w || sl_w)),
+              KGX_ERR_ARG, "kgx_spmm_gemm_ex4: a sliced launch needs 4 or 8 lists, their items, the sliced arrays, "
+                           "fix-up records and partials");
+  KGX_REQUIRE(n_classes == 0 || (!x2 && reduce == KGX_SUM && F_in == kFin && F_out % 16 == 0), KGX_ERR_UNSUPPORTED,
+              "kgx_spmm_gemm_ex4: the sliced schedule is implemented for one-table sums at F_in 128, F_out %% 16 == 0");
+  KGX_REQUIRE(n_classes == 0 || head_short_end <= n_short_end, KGX_ERR_ARG,
+              "kgx_spmm_gemm_ex4: head_short_end must not exceed n_short_end");
   KGX_REQUIRE(!x2 || (n_x1 >= 0 && n_x1 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(x2) % 16 == 0),
               KGX_ERR_ARG, "kgx_spmm_gemm: x2 must be 16-byte aligned and 0 <= n_x1 < 2^31");
   // (GIN's pre-scale reads the rows' own x: rows of the first table, local rows)
@@ -995,6 +1140,15 @@ extern "C" int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_
   a.relu = (flags & KGX_FUSED_RELU) != 0;
   a.cu_split = (flags & KGX_FUSED_CU_SPLIT) != 0;
   a.gin_scale = gin_scale;
+  a.sl_classes = items ? n_classes : 0;
+  a.sl_items = reinterpret_cast<const int4*>(sl_items);
+  a.sl_lists = reinterpret_cast<const int4*>(sl_lists);
+  a.sl_tiles = sl_tiles;
+  a.sl_idx = sl_idx;
+  a.sl_w = sl_w;
+  a.sl_split = reinterpret_cast<const int4*>(sl_split);
+  a.sl_n_split = sl_n_split;
+  a.sl_head_short_end = head_short_end;
   const bool wt = w != nullptr;
   if (x2) return wt ? launch<KGX_SUM, true, true>(a, stream) : launch<KGX_SUM, false, true>(a, stream);
   if (F_in < kFin || F_out % 16 != 0) {  // the masked instantiations (SAGEConv at C5: 100 -> 100)

@@ -122,6 +122,22 @@ _SIGNATURES = {
         _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
         _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
     ],
+    "kgx_spmm_gemm_ex4": [
+        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i64, _i32p, _i64,
+        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
+        _f32p, _i64, _f32p, _f32p, _i64,
+        _i32p, _i32p, _int, _i64, _i32p, _f32p, _i32p, _i64, _i64, ctypes.c_void_p,
+    ],
+    "kgx_slice_class": [ctypes.c_int32, _int],
+    "kgx_slice_grid": [_i64, _i64, _int],
+    "kgx_slice_count": [_i32p, _i64, _i32p, _i64, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                        ctypes.c_void_p],
+    "kgx_slice_workspace_bytes": [_i64, _i64, _int, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_slice_build": [
+        _i32p, _i32p, _f32p, _i32p, _i64, _i64, _i32p, _i64, _i64, ctypes.c_int32, _int,
+        _i32p, _f32p, _i32p, _i64, _i32p, _i32p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+    ],
     "kgx_spmm_max_backward": [
         _int, _int, _i32p, _i64, _i32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, ctypes.c_void_p,
     ],

@@ -354,19 +354,24 @@ def _partial_width(x: torch.Tensor) -> int:
 
 
 def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, flags, gin_scale,
-                  allow_split, n_long, tpack, tw, n_short_end, n_tiny2, dev):
+                  allow_split, n_long, tpack, tw, n_short_end, n_tiny2, dev, sl=None):
     """One fused aggregate -> transform launch into out (n_dst > 0 rows), and into
     agg, when given, the aggregated rows before the transform: the hub partials,
     the 256- / 128-wide dispatch, the CU-split decision and the native call.
     allow_split is off for the training forward's saved-aggregate launch: its
     tail launches also store the aggregated rows (the EXTRA instantiations), and
-    split it measured slower (NS training step 23.1 -> 25.0 ms, profiles/r05/train/)."""
+    split it measured slower (NS training step 23.1 -> 25.0 ms, profiles/r05/train/).
+    sl: a slice.SlicedSchedule for the main kernel (kgx_spmm_gemm_ex4), or None."""
     n_dst = rowptr.numel() - 1
     n_items = 0 if items is None else items.shape[0]
     n_split = 0 if split is None else split.shape[0]
+    if sl is not None and (items is None or x.shape[1] == F256 or x2 is not None):
+        sl = None
     partials = None
-    if items is not None and n_split > 0:
-        partials = torch.empty((n_slots, _partial_width(x)), dtype=torch.float32, device=dev)
+    if items is not None and (n_split > 0 or sl is not None):
+        # (the sliced launch falls back to the unsliced one when no grid fits: room for either schedule's slots)
+        slots = max(n_slots if n_split > 0 else 0, sl.n_slots if sl is not None else 0)
+        partials = torch.empty((slots, _partial_width(x)), dtype=torch.float32, device=dev)
     allow_split = allow_split and items is not None
     if x.shape[1] == F256:
         if tpack is not None and allow_split and _split_allowed(dev) and \
@@ -383,20 +388,25 @@ def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, 
         flags |= nat.FUSED_CU_SPLIT
         _count_cu_split()
     x2p, n_x1 = _x2_args(x, x2)
+    if sl is not None and ((w is not None) != (sl.w is not None) or sl.n_long != n_long):
+        sl = None  # (lists built without weights, or for another long-item boundary)
+    sl_args = (None, None, 0, 0, None, None, None, 0, -1) if sl is None else (
+        nat.ptr(sl.items), nat.ptr(sl.lists), sl.C, sl.tiles, nat.ptr(sl.col), nat.ptr(sl.w), nat.ptr(sl.fix),
+        sl.n_rows, min(sl.head_short_end, n_se))
     nat.check(
-        nat.lib().kgx_spmm_gemm_ex3(
+        nat.lib().kgx_spmm_gemm_ex4(
             reduce, nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, n_long, n_se, nat.ptr(tpack),
             nat.ptr(tw), n_tiny2, nat.ptr(split), n_split,
             nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), W.shape[1],
             nat.ptr(bias), flags, float(gin_scale), nat.ptr(out), out.stride(0), nat.ptr(partials),
-            nat.ptr(agg), agg.stride(0) if agg is not None else 0, nat.stream(dev),
+            nat.ptr(agg), agg.stride(0) if agg is not None else 0, *sl_args, nat.stream(dev),
         ),
         "kgx_spmm_gemm",
     )
 
 
 def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale, save_agg,
-                    relu=False, n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None):
+                    relu=False, n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None, sl=None):
     x, w, W, bias, x2 = _f32c(x), _f32c(w), _f32c(W), _f32c(bias), _f32c(x2)
     dev = nat.require_device(x, rowptr, rows, idx, w, W, bias, items, split, x2)
     n_dst = rowptr.numel() - 1
@@ -406,7 +416,7 @@ def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, b
         return out, agg
     flags = int(pre_gin) | (nat.FUSED_SHARE_GPU if _share_gpu() else 0) | (nat.FUSED_RELU if relu else 0)
     _fused_launch(out, agg if save_agg else None, x, x2, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias,
-                  flags, gin_scale, not save_agg, n_long, tpack, tw, n_short_end, n_tiny2, dev)
+                  flags, gin_scale, not save_agg, n_long, tpack, tw, n_short_end, n_tiny2, dev, sl)
     return out, agg
 
 
@@ -432,15 +442,33 @@ def spmm_gemm(
     n_short_end: int = -1,
     n_tiny2: int = 0,
     x2: Optional[torch.Tensor] = None,
+    sl_items: Optional[torch.Tensor] = None,
+    sl_lists: Optional[torch.Tensor] = None,
+    sl_idx: Optional[torch.Tensor] = None,
+    sl_w: Optional[torch.Tensor] = None,
+    sl_fix: Optional[torch.Tensor] = None,
+    sl_slots: int = 0,
+    sl_max_list: int = 0,
+    sl_head_short_end: int = -1,
 ) -> torch.Tensor:
-    """x2 (two-table gathers, kgx_spmm_gemm_ex3): sources >= x.shape[0] are rows of x2."""
+    """x2 (two-table gathers, kgx_spmm_gemm_ex3): sources >= x.shape[0] are rows of x2.
+    sl_*: a sliced schedule for the main kernel (slice.SlicedSchedule's arrays, kgx_spmm_gemm_ex4)."""
+    sl = None
+    if sl_items is not None:
+        from .slice import SlicedSchedule
+
+        sl = SlicedSchedule(T=0, C=sl_lists.shape[0], split_len=0, n_rows=sl_fix.shape[0], n_edges=sl_idx.numel(),
+                            n_items_s=0, n_long=n_long, col=sl_idx, w=sl_w, items=sl_items, lists=sl_lists,
+                            fix=sl_fix, n_slots=sl_slots, max_list=sl_max_list, build_ms=0.0,
+                            head_short_end=sl_head_short_end)
     return _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale,
-                           False, relu, n_long, tpack, tw, n_short_end, n_tiny2, x2)[0]
+                           False, relu, n_long, tpack, tw, n_short_end, n_tiny2, x2, sl)[0]
 
 
 @spmm_gemm.register_fake
 def _spmm_gemm_fake(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale, relu=False,
-                    n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None):
+                    n_long=-1, tpack=None, tw=None, n_short_end=-1, n_tiny2=0, x2=None, sl_items=None, sl_lists=None,
+                    sl_idx=None, sl_w=None, sl_fix=None, sl_slots=0, sl_max_list=0, sl_head_short_end=-1):
     return x.new_empty((rowptr.shape[0] - 1, W.shape[1]))
 
 
@@ -1074,14 +1102,37 @@ def _tiny_of(g, items):
     return tiny.tiny_pack(g)
 
 
-def _aggregate_transform_raw(g, x, W, red, weighted, bias, pre_gin, gin_scale, exact, relu=False, x2=None):
+def _slice_of(g, items, x, W, red, x2):
+    """The sliced schedule's arguments of kgx::spmm_gemm for this launch (slice.py:
+    built on the second forward over g), or the eight "none" values."""
+    from . import slice as S
+
+    none = (None, None, None, None, None, 0, 0, -1)
+    T, C, share = S.env_params()
+    if not S.slice_wanted(mode=S.env_mode(), default_on=S.DEFAULT_ON, have_items=items is not None,
+                          two_tables=x2 is not None, reduce=red, f_in=x.shape[1], f_out=W.shape[1],
+                          n_edges=int(g.col.numel()), T=T, C=C):
+        return none
+    if _share_gpu() or "accumulate_only" in g.extras or "restricted_of" in g.extras:
+        return none  # the sharded layers' passes and restricted sub-schedules keep the plain schedule
+    sl = S.sliced_schedule(g, T, C, share)
+    if sl is None:
+        return none
+    return sl.items, sl.lists, sl.col, sl.w, sl.fix, sl.n_slots, sl.max_list, sl.head_short_end
+
+
+def _aggregate_transform_raw(g, x, W, red, weighted, bias, pre_gin, gin_scale, exact, relu=False, x2=None,
+                             allow_slice=True):
     items, _, split, _, n_slots = g.work(exact)
     w = g.w if weighted else None
     if weighted and w is None:
         raise ValueError("graph was built without GCN normalisation weights")
+    sl = _slice_of(g, items if allow_slice else None, x, W, red, x2)
+    if sl[0] is not None and not weighted:
+        sl = sl[:3] + (None,) + sl[4:]
     return _timed(lambda: torch.ops.kgx.spmm_gemm(
         x, g.rowptr, g.rows, items, split, g.col, w, n_slots, red, W, bias, bool(pre_gin), float(gin_scale),
-        bool(relu), g.n_long if items is not None else -1, *_tiny_of(g, items), x2
+        bool(relu), g.n_long if items is not None else -1, *_tiny_of(g, items), x2, *sl
     ))
 
 
@@ -1162,7 +1213,8 @@ class _AggregateTransformFn(torch.autograd.Function):
                         count = torch.clamp(ctx.g.deg, max=1 << 24).float()
                         d = (grad_out / torch.clamp(count, min=1e-8).unsqueeze(1)).contiguous()
                     t = G.transpose(ctx.g)
-                    g_x = _aggregate_transform_raw(t, d, W_t, nat.SUM, ctx.weighted, None, False, 1.0, ctx.exact)
+                    g_x = _aggregate_transform_raw(t, d, W_t, nat.SUM, ctx.weighted, None, False, 1.0, ctx.exact,
+                                                   allow_slice=False)
                 else:
                     dP = grad_out @ W_t
                     g_x = _reduce_backward(ctx.g, ctx.red, ctx.weighted, False, x, dP, ctx.exact, ctx.x_rows)

@@ -1,6 +1,11 @@
 """Summarise rocprofv3 PMC passes into the per-launch HBM traffic bench.py reports.
 
-  python tools/pmc_summary.py FETCH_CSV WRITE_CSV OUT_JSON [--config ns]
+  python tools/pmc_summary.py FETCH_CSV WRITE_CSV OUT_JSON [--config ns] [--exclude REGEX]
+
+--exclude drops kernels whose full name matches REGEX: an instantiation that
+ran once before the steady state and is not part of a step (the unsliced main
+kernel of the first forward, before the sliced schedule exists), which would
+otherwise be summed with the one that is.
 
 FETCH_CSV / WRITE_CSV are rocprofv3 `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`
 counter_collection.csv files of the same bench.py command.  Per kernel the
@@ -81,13 +86,15 @@ def kernel_source_hash(kernel: str) -> str | None:
     return h.hexdigest()[:16]
 
 
-def per_kernel(path: str, counter: str) -> dict[str, float]:
+def per_kernel(path: str, counter: str, exclude: str | None = None) -> dict[str, float]:
     vals: dict[str, list[float]] = {}
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
             if r["Counter_Name"] != counter:
                 continue
             name = r["Kernel_Name"]
+            if exclude and re.search(exclude, name):
+                continue
             vals.setdefault(name, []).append(float(r["Counter_Value"]))
     return {k: statistics.median(v) for k, v in vals.items()}
 
@@ -100,8 +107,9 @@ def short(name: str) -> str:
 def main() -> None:
     fetch_csv, write_csv, out = sys.argv[1:4]
     config = sys.argv[sys.argv.index("--config") + 1] if "--config" in sys.argv else "ns"
-    fetch = per_kernel(fetch_csv, "FETCH_SIZE")
-    write = per_kernel(write_csv, "WRITE_SIZE")
+    exclude = sys.argv[sys.argv.index("--exclude") + 1] if "--exclude" in sys.argv else None
+    fetch = per_kernel(fetch_csv, "FETCH_SIZE", exclude)
+    write = per_kernel(write_csv, "WRITE_SIZE", exclude)
     kernels = {}
     for name in sorted(set(fetch) | set(write)):
         fk, wk = fetch.get(name), write.get(name)
