@@ -588,6 +588,69 @@ int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_row
                        const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused dot-product (query / key / value) graph attention: PyG's
+ * TransformerConv message passing without edge features, in one pass with an
+ * online segment softmax.  Destination row i, head h, edges e of the row
+ * (source j_e = col[e]):
+ *   s_e = scale * sum_c q[i,h,c] * k[j_e,h,c]
+ *   m = max_e s_e,  l = sum_e exp(s_e - m)          (no epsilon)
+ *   out[i,h,:] = sum_e exp(s_e - m) / l * mask_e * v[j_e,h,:]
+ * mask_e = kgx_dropout_mask(seed, drop_key[e], h) when drop_key is given, else 1.
+ * q: [n_dst, ld_q]; k, v: [n_src, ld_k], [n_src, ld_v]; fp32, unit column
+ * stride, separate leading dimensions (k and v may be the two column halves of
+ * one [n_src, 2*heads*channels] tensor).
+ * Work list as kgx_gatv2: items == NULL reduces every row of `rows` whole, in
+ * CSR order; otherwise split chunks write [H*C acc | H m | H l] to `partials`
+ * (n_slots * ld_p floats, ld_p = heads*channels + 2*heads rounded up to a
+ * multiple of 4) and a fix-up merges them in chunk order.
+ * stats (optional, [n_dst, 2*heads]): (m, l), kept for the backward.
+ * A row without edges is a zero row with stats (-inf, 0); a -inf score has
+ * weight 0; a (row, head) whose scores are all -inf, or that contains +inf or
+ * NaN, is NaN in its own block of `channels` columns only.  No atomics: a run
+ * gives the same bits every time.
+ * Errors, before any device work: KGX_ERR_UNSUPPORTED when heads *
+ * next_pow2(ceil(channels / K)) > 64 for the widest usable K channels per lane
+ * (8, 4 or 16 with 16-byte aligned pointers and leading dimensions that are
+ * multiples of 4, else 2 or 1); KGX_ERR_ARG for null pointers, bad sizes,
+ * ld < heads*channels, ld >= 2^31, drop_p outside [0, 1), and split rows
+ * without a split list or partials.
+ * ------------------------------------------------------------------------- */
+int kgx_dot_attention(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                      const int32_t* items, int64_t n_items,
+                      const int32_t* split, int64_t n_split,
+                      const int32_t* col, const float* q, int64_t ld_q, const float* k, int64_t ld_k,
+                      const float* v, int64_t ld_v, int heads, int channels, float scale,
+                      float* out, int64_t ld_out, float* partials, float* stats,
+                      const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Backward of kgx_dot_attention.  Needs the forward's `out` and `stats`.  With
+ * G = d loss / d out, D[i,h] = <G[i,h,:], out[i,h,:]>, p_e = exp(s_e - m) / l
+ * and ds_e = p_e * (mask_e * <G_i, v_j>_h - D[i,h]), two passes that both
+ * recompute p_e from q, k and stats:
+ *   destination pass (forward CSR + schedule): dsum_ws = D ([n_dst, heads]),
+ *     grad_q[i] = scale * sum_e ds_e * k[j_e];
+ *   source pass (transposed CSR + schedule; t_col = destination row, t_key =
+ *     input edge id of each transposed slot, the dropout key):
+ *     grad_v[j] = sum_e p_e * mask_e * G_i,  grad_k[j] = scale * sum_e ds_e * q_i.
+ * Split rows go through per-chunk partials summed in chunk order; partials:
+ * max(n_slots, t_n_slots) * 2*heads*channels floats.  No atomics and no
+ * E x heads buffer.  Errors as the forward's.
+ * ------------------------------------------------------------------------- */
+int kgx_dot_attention_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                               const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                               const int32_t* col, const float* q, int64_t ld_q, const float* k, int64_t ld_k,
+                               const float* v, int64_t ld_v, int heads, int channels, float scale,
+                               const float* out, int64_t ld_out, const float* stats,
+                               const float* grad_out, int64_t ld_grad,
+                               const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+                               const int32_t* t_items, int64_t t_n_items, const int32_t* t_split, int64_t t_n_split,
+                               const int32_t* t_col, const int32_t* t_key,
+                               float* grad_q, int64_t ld_gq, float* grad_k, int64_t ld_gk,
+                               float* grad_v, int64_t ld_gv, float* dsum_ws, float* partials,
+                               const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Fused segment softmax + weighted sum, the attention readouts' pooling (one
  * pass over x, online softmax; plus a fix-up for split segments):
  *   out[g,:] = sum_{i in g} softmax_g(s)_i * x[i,:]

@@ -20,6 +20,7 @@ from .layers import (
     PNAConv,
     SAGEConv,
     Set2Set,
+    TransformerConv,
     set_random_seed,
 )
 from .sampling import EdgeBatch, NegativeSampler, NeighborSampler, SampledBlocks, SampledSubgraph
@@ -48,6 +49,7 @@ __all__ = [
     "SampledBlocks",
     "SampledSubgraph",
     "Set2Set",
+    "TransformerConv",
     "add_self_loops",
     "batch_graphs",
     "build_csr",

@@ -21,6 +21,7 @@ from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
 from .sage_conv import SAGEConv
+from .transformer_conv import TransformerConv
 
 __all__ = [
     "Aggregator",
@@ -46,5 +47,6 @@ __all__ = [
     "Set2Set",
     "StdAggregator",
     "SumAggregator",
+    "TransformerConv",
     "set_random_seed",
 ]

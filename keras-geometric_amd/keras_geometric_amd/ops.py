@@ -7,6 +7,7 @@ torch.compile / symbolic tracing sees shapes without running the GPU.
   kgx::spmm   fused gather -> message -> segment {sum,mean,max,min,std} -> epilogue
   kgx::multi_aggr  several of those reducers from one gather, blocks concatenated
   kgx::gatv2  fused GATv2 attention aggregation
+  kgx::dot_attention  fused dot-product (query / key / value) attention aggregation
   kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
   kgx::edge_dot  edge scores from node rows (link prediction)
   kgx::gather_rows, kgx::scatter_f32   row movement helpers
@@ -670,6 +671,189 @@ def gatv2(
 def _gatv2_fake(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias, n_slots,
                 drop_key=None, drop_p=0.0, drop_seed=0):
     return h_src.new_empty((rowptr.shape[0] - 1, heads * channels))
+
+
+def _attn_table(t: torch.Tensor, width: int, what: str) -> torch.Tensor:
+    """A [n, heads*channels] fp32 table kgx_dot_attention reads in place: unit
+    column stride, non-overlapping rows (a column half of a wider tensor
+    passes through uncopied)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"kgx kernels compute in fp32; got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"dot_attention: {what} must be [n, {width}], got {tuple(t.shape)}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    return t
+
+
+def _attn_ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, save_stats,
+                        drop_key=None, drop_p=0.0, drop_seed=0):
+    HC = heads * channels
+    q, k, v = _attn_table(q, HC, "q"), _attn_table(k, HC, "k"), _attn_table(v, HC, "v")
+    dev = nat.require_device(q, k, v, rowptr, rows, col, items, split, drop_key)
+    n_dst = rowptr.numel() - 1
+    if q.shape[0] != n_dst or k.shape[0] != v.shape[0]:
+        raise ValueError(f"dot_attention: q has {q.shape[0]} rows for {n_dst} destinations, k {k.shape[0]} and v "
+                         f"{v.shape[0]} rows")
+    out = torch.empty((n_dst, HC), dtype=torch.float32, device=dev)
+    stats = torch.empty((n_dst if save_stats else 0, 2 * heads), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return out, stats
+    n_items = 0 if items is None else items.shape[0]
+    n_split = 0 if split is None else split.shape[0]
+    partials = None
+    if items is not None and n_split > 0:
+        # per slot [HC acc | heads m | heads l], padded to whole float4s (kgx.h)
+        partials = torch.empty((n_slots, (HC + 2 * heads + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_dot_attention(
+            nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
+            nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), heads, channels,
+            float(scale), nat.ptr(out), out.stride(0), nat.ptr(partials), nat.ptr(stats) if save_stats else None,
+            nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p), int(drop_seed) & (2**64 - 1),
+            nat.stream(dev),
+        ),
+        "kgx_dot_attention",
+    )
+    return out, stats
+
+
+@torch.library.custom_op("kgx::dot_attention_save", mutates_args=())
+def dot_attention_save(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    heads: int,
+    channels: int,
+    scale: float,
+    n_slots: int,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """kgx::dot_attention that also returns the per-row softmax statistics [n_dst, 2*heads]: (m, l)."""
+    return _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, True,
+                               drop_key, drop_p, drop_seed)
+
+
+@dot_attention_save.register_fake
+def _dot_attention_save_fake(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots,
+                             drop_key=None, drop_p=0.0, drop_seed=0):
+    n = rowptr.shape[0] - 1
+    return q.new_empty((n, heads * channels)), q.new_empty((n, 2 * heads))
+
+
+@torch.library.custom_op("kgx::dot_attention", mutates_args=())
+def dot_attention_op(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    heads: int,
+    channels: int,
+    scale: float,
+    n_slots: int,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> torch.Tensor:
+    """out[i,h,:] = sum_e softmax_i(scale <q_i, k_j>_h)_e mask_e v[j_e,h,:] (kgx_dot_attention)."""
+    return _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, False,
+                               drop_key, drop_p, drop_seed)[0]
+
+
+@dot_attention_op.register_fake
+def _dot_attention_fake(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, drop_key=None,
+                        drop_p=0.0, drop_seed=0):
+    return q.new_empty((rowptr.shape[0] - 1, heads * channels))
+
+
+@torch.library.custom_op("kgx::dot_attention_backward", mutates_args=())
+def dot_attention_backward(
+    grad_out: torch.Tensor,
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    out: torch.Tensor,
+    stats: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_key: torch.Tensor,
+    t_slots: int,
+    heads: int,
+    channels: int,
+    scale: float,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_q, grad_k, grad_v) of kgx::dot_attention_save: a destination pass
+    over the forward CSR and a source pass over the transposed one, both
+    recomputing the probabilities from q, k and stats (kgx_dot_attention_backward)."""
+    HC = heads * channels
+    q, k, v = _attn_table(q, HC, "q"), _attn_table(k, HC, "k"), _attn_table(v, HC, "v")
+    grad_out, out, stats = _f32c(grad_out), _f32c(out), _f32c(stats)
+    dev = nat.require_device(grad_out, q, k, v, out, stats, rowptr, rows, items, split, col, t_rowptr, t_rows,
+                             t_items, t_split, t_col, t_key, drop_key)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    g_q = torch.empty((n_dst, HC), dtype=torch.float32, device=dev)
+    g_k = torch.empty((n_src, HC), dtype=torch.float32, device=dev)
+    g_v = torch.empty((n_src, HC), dtype=torch.float32, device=dev)
+    if col.numel() == 0 or n_dst == 0 or n_src == 0:
+        return g_q.zero_(), g_k.zero_(), g_v.zero_()
+    dsum = torch.empty((n_dst, heads), dtype=torch.float32, device=dev)
+    n_items = 0 if items is None else items.shape[0]
+    n_split = 0 if split is None else split.shape[0]
+    t_n_items = 0 if t_items is None else t_items.shape[0]
+    t_n_split = 0 if t_split is None else t_split.shape[0]
+    partials = None
+    if (items is not None and n_split > 0) or (t_items is not None and t_n_split > 0):
+        partials = torch.empty((max(n_slots, t_slots, 1), 2 * HC), dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_dot_attention_backward(
+            nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
+            nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), heads, channels,
+            float(scale), nat.ptr(out), out.stride(0), nat.ptr(stats), nat.ptr(grad_out), grad_out.stride(0),
+            nat.ptr(t_rowptr), nat.ptr(t_rows), n_src, nat.ptr(t_items), t_n_items, nat.ptr(t_split), t_n_split,
+            nat.ptr(t_col), nat.ptr(t_key), nat.ptr(g_q), g_q.stride(0), nat.ptr(g_k), g_k.stride(0),
+            nat.ptr(g_v), g_v.stride(0), nat.ptr(dsum), nat.ptr(partials),
+            nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p), int(drop_seed) & (2**64 - 1),
+            nat.stream(dev),
+        ),
+        "kgx_dot_attention_backward",
+    )
+    return g_q, g_k, g_v
+
+
+@dot_attention_backward.register_fake
+def _dot_attention_backward_fake(grad_out, q, k, v, out, stats, rowptr, rows, items, split, col, n_slots, t_rowptr,
+                                 t_rows, t_items, t_split, t_col, t_key, t_slots, heads, channels, scale,
+                                 drop_key=None, drop_p=0.0, drop_seed=0):
+    hc = heads * channels
+    return (q.new_empty((rowptr.shape[0] - 1, hc)), q.new_empty((t_rowptr.shape[0] - 1, hc)),
+            q.new_empty((t_rowptr.shape[0] - 1, hc)))
 
 
 @torch.library.custom_op("kgx::gather_rows", mutates_args=())
@@ -1394,6 +1578,77 @@ def gatv2_aggregate(
         return _GATv2Fn.apply(h_src, h_dst, att, bias, g, heads, channels, negative_slope, exact, float(dropout),
                               int(seed))
     return _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, float(dropout), int(seed))
+
+
+def _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, drop_p=0.0, drop_seed=0):
+    items, _, split, _, n_slots = g.work(exact)
+    return _timed(lambda: torch.ops.kgx.dot_attention(
+        q, k, v, g.rowptr, g.rows, items, split, g.col, heads, channels, float(scale), n_slots,
+        g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+    ))
+
+
+class _DotAttentionFn(torch.autograd.Function):
+    """Autograd of the fused dot-product attention: the forward keeps its
+    output and per-row softmax statistics; kgx_dot_attention_backward runs a
+    destination pass (D, d q) over the forward CSR and a source pass (d k, d v)
+    over the transposed CSR, both recomputing the probabilities, hub rows split
+    into chunks, no atomics."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, g, heads, channels, scale, exact, drop_p, drop_seed):
+        ctx.g, ctx.heads, ctx.channels, ctx.scale, ctx.exact = g, heads, channels, float(scale), exact
+        ctx.drop_p, ctx.drop_seed = drop_p, drop_seed
+        items, _, split, _, n_slots = g.work(exact)
+        out, stats = _timed(lambda: torch.ops.kgx.dot_attention_save(
+            q, k, v, g.rowptr, g.rows, items, split, g.col, heads, channels, float(scale), n_slots,
+            g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+        ))
+        ctx.save_for_backward(q, k, v, out, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        q, k, v, out, stats = ctx.saved_tensors
+        g = ctx.g
+        t = G.transpose(g)
+        items, _, split, _, n_slots = g.work(ctx.exact)
+        t_items, _, t_split, _, t_slots = t.work(ctx.exact)
+        g_q, g_k, g_v = _timed(lambda: torch.ops.kgx.dot_attention_backward(
+            grad_out, q, k, v, out, stats, g.rowptr, g.rows, items, split, g.col, n_slots,
+            t.rowptr, t.rows, t_items, t_split, t.col, t.eid, t_slots, ctx.heads, ctx.channels, ctx.scale,
+            g.eid if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed),
+        ))
+        return g_q, g_k, g_v, None, None, None, None, None, None, None
+
+
+def dot_attention(
+    g: CSRGraph,
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    heads: int,
+    channels: int,
+    *,
+    scale: float | None = None,
+    exact: bool = False,
+    dropout: float = 0.0,
+    seed: int = 0,
+) -> torch.Tensor:
+    """Fused dot-product graph attention (TransformerConv's message passing):
+    out[i,h,:] = sum_{e: j_e -> i} softmax_i(scale <q_i, k_j>_h)_e v[j_e,h,:];
+    q [n_dst, heads*channels], k and v [n_src, heads*channels] (row views of a
+    wider tensor are read in place).  scale=None: 1/sqrt(channels).
+    Differentiable in q, k and v.  dropout > 0: attention dropout of the
+    normalised weight per (edge, head), mask of (seed, input edge id, head)."""
+    import math
+
+    scale = 1.0 / math.sqrt(channels) if scale is None else float(scale)
+    if _needs_grad(q, k, v):
+        return _DotAttentionFn.apply(q, k, v, g, heads, channels, scale, exact, float(dropout), int(seed))
+    return _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, float(dropout), int(seed))
 
 
 # ---------------------------------------------------------------------------
