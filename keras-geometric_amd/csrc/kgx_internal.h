@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kgx.h"
+#include "kgx_attn_layout.h"  // next_pow2, log2i
 
 namespace kgx {
 
@@ -305,18 +306,6 @@ struct SplitJoin {
   }
   ~SplitJoin() { (void)join(); }
 };
-
-
-inline int next_pow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-inline int log2i(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
 
 }  // namespace kgx
 

@@ -22,8 +22,7 @@
 // merged in chunk order by a fix-up, so results are the same bits every run.
 // There is no epsilon in the denominator (the reference's softmax has none):
 // an empty segment is a zero row, an all -inf segment is NaN, as torch.softmax.
-#include "kgx_internal.h"
-#include "kgx_vec.h"
+#include "kgx_attn.h"
 
 namespace kgx {
 namespace {
@@ -31,13 +30,7 @@ namespace {
 constexpr int kPoolMaxF = KGX_POOL_MAX_F;
 
 struct PoolArgs {
-  const int32_t* rowptr;
-  const int32_t* rows;
-  int64_t n_rows;
-  const int4* items;
-  int64_t n_items;
-  const int4* split;
-  int64_t n_split;
+  Sched sched;
   const int32_t* idx;  // node per segment slot, or null: identity
   const float* x;
   int64_t ld_x;
@@ -53,22 +46,6 @@ struct PoolArgs {
   float* partials;  // per slot: [F acc | m | l]
   int G, lgG;
 };
-
-// Sum over the G (power of two) lanes of a group, result in every lane: DPP
-// moves within 16 lanes, shuffles above (gatv2.hip's head_reduce).
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float group_reduce(float p, int G) {
-  if (G > 1) p += dpp<0xB1>(p);   // quad_perm [1,0,3,2]
-  if (G > 2) p += dpp<0x4E>(p);   // quad_perm [2,3,0,1]
-  if (G > 4) p += dpp<0x141>(p);  // row_half_mirror
-  if (G > 8) p += dpp<0x140>(p);  // row_mirror
-  if (G > 16) p += __shfl_xor(p, 16, 64);
-  if (G > 32) p += __shfl_xor(p, 32, 64);
-  return p;
-}
 
 // The shift of the online softmax: the running max, or 0 while it is still
 // -inf (nothing but -inf scores seen: every weight so far is exp(-inf) = 0,
@@ -117,28 +94,17 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_kernel(PoolArgs a) {
   const int G = a.G;
   const int lane = threadIdx.x & (G - 1);
   const Lanes<V, R> L(lane, G, a.F);
-  const int64_t ngroups = (int64_t(gridDim.x) * kBlock) >> a.lgG;
-  const int64_t n_work = a.items ? a.n_items : a.n_rows;
+  const int64_t ngroups = group_count(a.lgG);
+  const int64_t n_work = a.sched.n_work();
 
   float su[W];
 #pragma unroll
   for (int k = 0; k < W; ++k) su[k] = 0.0f;
   if (a.u) L.load(su, a.u);
 
-  for (int64_t it = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> a.lgG; it < n_work; it += ngroups) {
+  for (int64_t it = first_group(a.lgG); it < n_work; it += ngroups) {
     int32_t row, beg, end, slot;
-    if (a.items) {
-      const int4 v = a.items[it];
-      row = v.x;
-      beg = v.y;
-      end = v.z;
-      slot = v.w;
-    } else {
-      row = a.rows[it];
-      beg = a.rowptr[row];
-      end = a.rowptr[row + 1];
-      slot = -1;
-    }
+    work_item(a.sched, it, row, beg, end, slot);
     const float cg = a.u ? a.c[row] : 0.0f;
     double acc[W];
 #pragma unroll
@@ -284,9 +250,9 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_fixup_kernel(PoolArgs a) 
   const int G = a.G;
   const int lane = threadIdx.x & (G - 1);
   const Lanes<V, R> L(lane, G, a.F);
-  const int64_t ngroups = (int64_t(gridDim.x) * kBlock) >> a.lgG;
-  for (int64_t it = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> a.lgG; it < a.n_split; it += ngroups) {
-    const int4 sp = a.split[it];
+  const int64_t ngroups = group_count(a.lgG);
+  for (int64_t it = first_group(a.lgG); it < a.sched.n_split; it += ngroups) {
+    const int4 sp = a.sched.split[it];
     float M = -__builtin_inff();
     double Lsum = 0.0, acc[W];
 #pragma unroll
@@ -311,8 +277,8 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_fixup_block_kernel(PoolAr
   const int grp = threadIdx.x >> a.lgG;
   const int n_grp = kBlock >> a.lgG;
   const Lanes<V, R> L(lane, G, a.F);
-  for (int64_t it = blockIdx.x; it < a.n_split; it += gridDim.x) {
-    const int4 sp = a.split[it];
+  for (int64_t it = blockIdx.x; it < a.sched.n_split; it += gridDim.x) {
+    const int4 sp = a.sched.split[it];
     const int32_t nc = sp.z;
     const int32_t per = (nc + n_grp - 1) / n_grp;
     const int32_t c_beg = grp * per < nc ? grp * per : nc;
@@ -350,22 +316,17 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_fixup_block_kernel(PoolAr
 
 template <int V, int R>
 int launch(const PoolArgs& a, hipStream_t s) {
-  const int64_t work = a.items ? a.n_items : a.n_rows;
-  if (work > 0) {
-    auto k = softmax_pool_kernel<V, R>;
-    hipLaunchKernelGGL(k, dim3(resident_grid(k, work, a.G)), dim3(kBlock), 0, s, a);
-    KGX_CHECK_LAUNCH();
-  }
-  if (a.items && a.n_split > 0) {
+  if (const int rc = launch_resident(softmax_pool_kernel<V, R>, a.sched.n_work(), a.G, a, s)) return rc;
+  if (a.sched.n_split > 0) {
     // a block per segment once the split segments average (at most n_items / n_split chunks each)
     // four merge steps per lane group of a block; a lane group per segment below that
     const int64_t n_grp = kBlock / a.G;
-    if (a.n_items / a.n_split >= 4 * n_grp) {
+    if (a.sched.n_items / a.sched.n_split >= 4 * n_grp) {
       auto k = softmax_pool_fixup_block_kernel<V, R>;
-      hipLaunchKernelGGL(k, dim3(resident_grid(k, a.n_split, kBlock)), dim3(kBlock), 0, s, a);
+      hipLaunchKernelGGL(k, dim3(resident_grid(k, a.sched.n_split, kBlock)), dim3(kBlock), 0, s, a);
     } else {
       auto k = softmax_pool_fixup_kernel<V, R>;
-      hipLaunchKernelGGL(k, dim3(resident_grid(k, a.n_split, a.G)), dim3(kBlock), 0, s, a);
+      hipLaunchKernelGGL(k, dim3(resident_grid(k, a.sched.n_split, a.G)), dim3(kBlock), 0, s, a);
     }
     KGX_CHECK_LAUNCH();
   }
@@ -386,8 +347,6 @@ inline Layout layout_for(int64_t F, bool vec4) {
   y.G = next_pow2((vecs + y.R - 1) / y.R);
   return y;
 }
-
-inline bool aligned(const void* p, int b) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % b == 0; }
 
 }  // namespace
 }  // namespace kgx
@@ -412,22 +371,14 @@ extern "C" int kgx_softmax_pool(const int32_t* rowptr, const int32_t* rows, int6
               "kgx_softmax_pool: KGX_POOL_SCORE_TANH applies to fused scores only");
   KGX_REQUIRE(ld_x >= F && ld_out >= F, KGX_ERR_ARG, "kgx_softmax_pool: leading dimension < F");
   KGX_REQUIRE(ld_x < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_softmax_pool: leading dimension >= 2^31");
-  const bool use_items = items != nullptr;
-  KGX_REQUIRE(!use_items || n_split == 0 || (split && partials), KGX_ERR_ARG,
+  KGX_REQUIRE(!items || n_split == 0 || (split && partials), KGX_ERR_ARG,
               "kgx_softmax_pool: split rows need split list and partials");
   KGX_REQUIRE(F <= kPoolMaxF, KGX_ERR_UNSUPPORTED, "kgx_softmax_pool: F=%lld above the maximum %d (unsupported)",
               (long long)F, kPoolMaxF);
-  const bool vec4 = F % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && aligned(x, 16) && aligned(out, 16) &&
-                    aligned(score_u, 16);
+  const bool vec4 = attn_vec_ok(16, {x, out, score_u}, {F, ld_x, ld_out});
   const Layout y = layout_for(F, vec4);
   PoolArgs a{};
-  a.rowptr = rowptr;
-  a.rows = rows;
-  a.n_rows = n_seg;
-  a.items = use_items ? reinterpret_cast<const int4*>(items) : nullptr;
-  a.n_items = use_items ? n_items : 0;
-  a.split = reinterpret_cast<const int4*>(split);
-  a.n_split = use_items ? n_split : 0;
+  a.sched = make_sched(rowptr, rows, n_seg, items, n_items, split, n_split);
   a.idx = idx;
   a.x = x;
   a.ld_x = ld_x;
@@ -488,8 +439,8 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_bwd_kernel(PoolBwdArgs a)
   const int G = a.G;
   const int lane = threadIdx.x & (G - 1);
   const Lanes<V, R> L(lane, G, a.F);
-  const int64_t ngroups = (int64_t(gridDim.x) * kBlock) >> a.lgG;
-  for (int64_t i = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> a.lgG; i < a.N; i += ngroups) {
+  const int64_t ngroups = group_count(a.lgG);
+  for (int64_t i = first_group(a.lgG); i < a.N; i += ngroups) {
     const int32_t g = a.seg ? a.seg[i] : 0;
     const bool in = g >= 0 && g < a.n_seg;  // ids outside the segments pool nowhere: zero gradient
     const int64_t gc = in ? g : 0;
@@ -514,10 +465,7 @@ __global__ __launch_bounds__(kBlock) void softmax_pool_bwd_kernel(PoolBwdArgs a)
 
 template <int V, int R>
 int launch_bwd(const PoolBwdArgs& a, hipStream_t s) {
-  auto k = softmax_pool_bwd_kernel<V, R>;
-  hipLaunchKernelGGL(k, dim3(resident_grid(k, a.N, a.G)), dim3(kBlock), 0, s, a);
-  KGX_CHECK_LAUNCH();
-  return KGX_OK;
+  return launch_resident(softmax_pool_bwd_kernel<V, R>, a.N, a.G, a, s);
 }
 
 }  // namespace
@@ -537,8 +485,7 @@ extern "C" int kgx_softmax_pool_backward(int64_t N, int64_t n_seg, const int32_t
               "kgx_softmax_pool_backward: leading dimension < F");
   KGX_REQUIRE(F <= kPoolMaxF, KGX_ERR_UNSUPPORTED,
               "kgx_softmax_pool_backward: F=%lld above the maximum %d (unsupported)", (long long)F, kPoolMaxF);
-  const bool vec4 = F % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && ld_grad % 4 == 0 && ld_grad_x % 4 == 0 &&
-                    aligned(x, 16) && aligned(out, 16) && aligned(grad_out, 16) && aligned(grad_x, 16);
+  const bool vec4 = attn_vec_ok(16, {x, out, grad_out, grad_x}, {F, ld_x, ld_out, ld_grad, ld_grad_x});
   const Layout y = layout_for(F, vec4);
   PoolBwdArgs a{};
   a.N = N;

@@ -584,6 +584,25 @@ def fused_sage_supported(f_in: int, f_out: int) -> bool:
     return 0 < f_in <= 128 and f_in % 4 == 0 and 0 < f_out <= 128 and f_out % 4 == 0
 
 
+def _sched_counts(items, split):
+    """(n_items, n_split) of a schedule's lists, 0 for a list that is absent."""
+    return (0 if items is None else items.shape[0]), (0 if split is None else split.shape[0])
+
+
+def _attn_partials(dev, items, n_split, n_slots, heads, channels):
+    """Chunk partials of the attention forwards, None without split rows: per
+    slot [H*C acc | H m | H l], padded to whole float4s (attn_partial_ld in
+    csrc/kgx_attn_layout.h; tests/test_attn_layout_host.py holds the two equal)."""
+    if items is None or n_split == 0:
+        return None
+    return torch.empty((n_slots, (heads * channels + 2 * heads + 3) // 4 * 4), dtype=torch.float32, device=dev)
+
+
+def _drop_args(drop_key, drop_p, drop_seed):
+    """(key pointer, p, seed) as the C entry points take attention dropout: no key without dropout."""
+    return (nat.ptr(drop_key) if drop_p > 0 else None), float(drop_p), int(drop_seed) & (2**64 - 1)
+
+
 def _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias,
                 n_slots, save_stats, drop_key=None, drop_p=0.0, drop_seed=0):
     h_src, h_dst, att, bias = _f32c(h_src), _f32c(h_dst), _f32c(att), _f32c(bias)
@@ -594,19 +613,14 @@ def _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, chann
     stats = torch.empty((n_dst if save_stats else 0, 2 * heads), dtype=torch.float32, device=dev)
     if n_dst == 0:
         return out, stats
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    partials = None
-    if items is not None and n_split > 0:
-        # per slot [HC acc | heads m | heads l], padded to whole float4s (kgx.h)
-        partials = torch.empty((n_slots, (HC + 2 * heads + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    n_items, n_split = _sched_counts(items, split)
+    partials = _attn_partials(dev, items, n_split, n_slots, heads, channels)
     nat.check(
         nat.lib().kgx_gatv2(
             nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split,
             nat.ptr(col), nat.ptr(h_src), nat.ptr(h_dst), h_src.stride(0), nat.ptr(att), heads, channels,
             float(negative_slope), nat.ptr(out), out.stride(0), nat.ptr(bias), nat.ptr(partials),
-            nat.ptr(stats) if save_stats else None, nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p),
-            int(drop_seed) & (2**64 - 1), nat.stream(dev),
+            nat.ptr(stats) if save_stats else None, *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
         ),
         "kgx_gatv2",
     )
@@ -703,19 +717,14 @@ def _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channel
     stats = torch.empty((n_dst if save_stats else 0, 2 * heads), dtype=torch.float32, device=dev)
     if n_dst == 0:
         return out, stats
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    partials = None
-    if items is not None and n_split > 0:
-        # per slot [HC acc | heads m | heads l], padded to whole float4s (kgx.h)
-        partials = torch.empty((n_slots, (HC + 2 * heads + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    n_items, n_split = _sched_counts(items, split)
+    partials = _attn_partials(dev, items, n_split, n_slots, heads, channels)
     nat.check(
         nat.lib().kgx_dot_attention(
             nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
             nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), heads, channels,
             float(scale), nat.ptr(out), out.stride(0), nat.ptr(partials), nat.ptr(stats) if save_stats else None,
-            nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p), int(drop_seed) & (2**64 - 1),
-            nat.stream(dev),
+            *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
         ),
         "kgx_dot_attention",
     )
@@ -824,10 +833,8 @@ def dot_attention_backward(
     if col.numel() == 0 or n_dst == 0 or n_src == 0:
         return g_q.zero_(), g_k.zero_(), g_v.zero_()
     dsum = torch.empty((n_dst, heads), dtype=torch.float32, device=dev)
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    t_n_items = 0 if t_items is None else t_items.shape[0]
-    t_n_split = 0 if t_split is None else t_split.shape[0]
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
     partials = None
     if (items is not None and n_split > 0) or (t_items is not None and t_n_split > 0):
         partials = torch.empty((max(n_slots, t_slots, 1), 2 * HC), dtype=torch.float32, device=dev)
@@ -839,8 +846,7 @@ def dot_attention_backward(
             nat.ptr(t_rowptr), nat.ptr(t_rows), n_src, nat.ptr(t_items), t_n_items, nat.ptr(t_split), t_n_split,
             nat.ptr(t_col), nat.ptr(t_key), nat.ptr(g_q), g_q.stride(0), nat.ptr(g_k), g_k.stride(0),
             nat.ptr(g_v), g_v.stride(0), nat.ptr(dsum), nat.ptr(partials),
-            nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p), int(drop_seed) & (2**64 - 1),
-            nat.stream(dev),
+            *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
         ),
         "kgx_dot_attention_backward",
     )
@@ -1538,10 +1544,8 @@ class _GATv2Fn(torch.autograd.Function):
         if slot is None:
             slot = t.extras["fwd_slot"].to(torch.int32)
             t.extras["fwd_slot32"] = slot
-        n_items = 0 if items is None else items.shape[0]
-        n_split = 0 if split is None else split.shape[0]
-        t_n_items = 0 if t_items is None else t_items.shape[0]
-        t_n_split = 0 if t_split is None else t_split.shape[0]
+        n_items, n_split = _sched_counts(items, split)
+        t_n_items, t_n_split = _sched_counts(t_items, t_split)
         nat.check(
             nat.lib().kgx_gatv2_backward(
                 nat.ptr(g.rowptr), nat.ptr(g.rows), g.n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split,
@@ -1550,8 +1554,7 @@ class _GATv2Fn(torch.autograd.Function):
                 grad_out.stride(0), nat.ptr(t.rowptr), nat.ptr(t.rows), g.n_src, nat.ptr(t_items), t_n_items,
                 nat.ptr(t_split), t_n_split, nat.ptr(t.col), nat.ptr(slot), nat.ptr(g_src), nat.ptr(g_dst),
                 g_src.stride(0), nat.ptr(g_att), nat.ptr(alpha), nat.ptr(ds), nat.ptr(partials),
-                nat.ptr(g.eid) if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed) & (2**64 - 1),
-                nat.stream(dev),
+                *_drop_args(g.eid, ctx.drop_p, ctx.drop_seed), nat.stream(dev),
             ),
             "kgx_gatv2_backward",
         )
@@ -1785,8 +1788,7 @@ def _softmax_pool_impl(x, rowptr, rows, items, split, idx, s, score_u, score_c, 
     s_out = torch.zeros(N if fused else 0, dtype=torch.float32, device=dev)
     if n_seg == 0:
         return out, stats, s_out
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
+    n_items, n_split = _sched_counts(items, split)
     partials = None
     if items is not None and n_split > 0:
         partials = torch.empty((n_slots, F + 2), dtype=torch.float32, device=dev)

@@ -20,8 +20,8 @@ the scale of the bound a re-associated fp32 sum is held to,
 
 The module also owns what the CPU and GPU test modules share: the graphs
 (gatv2_ref.make_graph's, reused by import), the (heads, channels) list with
-the lane layout csrc/dot_attention.hip gives each pair, a Python mirror of
-that dispatch, and the seeded inputs.
+the lane layout kgx_dot_attention gives each pair (gatv2_ref.fwd_layout, the
+Python mirror of the forward rule), and the seeded inputs.
 """
 
 from __future__ import annotations
@@ -36,8 +36,8 @@ from gatv2_ref import DOMINANT_POS, HUB_DST, HUB_SRC, SPLIT_LEN, dominant_graph,
 
 TOL = 1e-5
 
-# (heads, channels): (K, LH) = channels per lane and lanes per head, as csrc/dot_attention.hip's
-# pick_k gives them for aligned contiguous inputs (one rule for the forward and both backward passes)
+# (heads, channels): (K, LH) = channels per lane and lanes per head, as csrc/kgx_attn_layout.h's
+# attn_pick_k gives them for aligned contiguous inputs (one rule for the forward and both backward passes)
 LAYOUTS = {
     (8, 16): (8, 2),
     (8, 64): (8, 8),
@@ -57,23 +57,7 @@ DOMINANT_SRC = GR.DOMINANT_SRC
 DOMINANT_GAP = 30.0  # the dominant edge's score exceeds every other of its row by about this much
 
 
-def _np2(v: int) -> int:
-    return 1 << (max(int(v), 1) - 1).bit_length()
-
-
-def layout(heads: int, channels: int, ld: int | None = None, aligned: int = 16):
-    """(K, LH) of kgx_dot_attention and kgx_dot_attention_backward for tensors
-    whose pointers are `aligned`-byte aligned and whose leading dimensions are
-    all multiples of gcd(ld, 4) (ld defaults to heads * channels), or None for
-    an unsupported shape (more than 64 lanes per row)."""
-    ld = heads * channels if ld is None else ld
-    if ld % 4 == 0 and aligned % 16 == 0:
-        for k in (8, 4, 16):
-            if channels % k == 0 and heads * _np2(channels // k) <= 64:
-                return k, _np2(channels // k)
-    k = 2 if (channels % 2 == 0 and ld % 2 == 0 and aligned % 8 == 0) else 1
-    lh = _np2((channels + k - 1) // k)
-    return (k, lh) if heads * lh <= 64 else None
+layout = GR.fwd_layout  # (K, LH) of kgx_dot_attention and kgx_dot_attention_backward, or None
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,8 +22,9 @@ d att all sum these terms in another order than the reference.
 
 The module also owns what the CPU and the GPU test module must share: the two
 bipartite graphs, the (heads, channels) list with the lane layout the two
-dispatchers of csrc/gatv2.hip give each pair, a Python mirror of those
-dispatch rules, and the seeded inputs.
+rules of csrc/kgx_attn_layout.h give each pair, a Python mirror of those rules
+(held equal to the C++ by tests/test_attn_layout_host.py), and the seeded
+inputs.
 """
 
 from __future__ import annotations
@@ -44,8 +45,9 @@ GRAPHS = {
     "deep": (500, 400, 6000, 1000, 2500, 102),
 }
 
-# (heads, channels): (forward K, backward K) = channels per lane, as csrc/gatv2.hip picks them
-# for aligned contiguous inputs (fwd_layout / bwd_layout below mirror the rules)
+# (heads, channels): (forward K, backward K) = channels per lane, as kgx_gatv2 and
+# kgx_gatv2_backward pick them for aligned contiguous inputs (fwd_layout / bwd_layout
+# below mirror the rules); the remarks name what each pair is in the list for
 LAYOUTS = {
     (8, 16): (8, 2),
     (8, 32): (8, 4),
@@ -75,28 +77,36 @@ def _np2(v: int) -> int:
     return 1 << (max(int(v), 1) - 1).bit_length()
 
 
-def fwd_layout(heads: int, channels: int):
-    """(K, LH) of kgx_gatv2 for contiguous 16-byte aligned tensors (row stride
-    heads * channels), or None for an unsupported shape."""
-    ld = heads * channels
-    if ld % 4 == 0:
+def fwd_layout(heads: int, channels: int, ld: int | None = None, aligned: int = 16):
+    """(K, LH) of the forward rule (attn_pick_k: kgx_gatv2, kgx_dot_attention and
+    kgx_dot_attention_backward) for tensors whose pointers are `aligned`-byte
+    aligned and whose leading dimensions are all multiples of gcd(ld, 4) (ld
+    defaults to heads * channels), or None for an unsupported shape (more than
+    64 lanes per row)."""
+    ld = heads * channels if ld is None else ld
+    if ld % 4 == 0 and aligned % 16 == 0:
         for k in (8, 4, 16):
             if channels % k == 0 and heads * _np2(channels // k) <= 64:
                 return k, _np2(channels // k)
-    k = 2 if channels % 2 == 0 and ld % 2 == 0 else 1
+    k = 2 if (channels % 2 == 0 and ld % 2 == 0 and aligned % 8 == 0) else 1
     lh = _np2((channels + k - 1) // k)
     return (k, lh) if heads * lh <= 64 else None
 
 
-def bwd_layout(heads: int, channels: int):
-    """(K, LH) of kgx_gatv2_backward under the same conditions."""
-    ld = heads * channels
+def bwd_layout(heads: int, channels: int, ld: int | None = None, aligned: int = 16):
+    """(K, LH) of kgx_gatv2_backward (attn_pick_k_smallest) under the same conditions."""
+    ld = heads * channels if ld is None else ld
     for k in (1, 2, 4, 8, 16):
-        if channels % k or ld % min(k, 4):
+        if channels % k or ld % min(k, 4) or aligned % (4 * min(k, 4)):
             continue
         if heads * _np2(channels // k) <= 64:
             return k, _np2(channels // k)
     return None
+
+
+def group_lanes(heads: int, layout):
+    """G, the lanes of a row's group, of a (K, LH) layout."""
+    return _np2(heads * layout[1])
 
 
 @functools.lru_cache(maxsize=None)

@@ -15,8 +15,9 @@ any kernel is judged by it (tests/test_gpu_gatv2_op.py).
   of the float64 one: out within 0.5 * 1e-5 max(1, |ref|), d h_src / d h_dst /
   d att within 0.5 * 1e-5 max(1, A).  Measured maxima over all pairs (this
   file, `pytest -s`): out 0.27, d h_src 0.26, d h_dst 0.17, d att 0.02.
-* The shape list reaches every channels-per-lane K of both dispatchers of
-  csrc/gatv2.hip, mirrored in gatv2_ref.fwd_layout / bwd_layout.
+* The shape list reaches every channels-per-lane K of both rules of
+  csrc/kgx_attn_layout.h, mirrored in gatv2_ref.fwd_layout / bwd_layout
+  (tests/test_attn_layout_host.py holds the mirrors equal to the C++).
 """
 
 from __future__ import annotations

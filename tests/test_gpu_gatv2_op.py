@@ -17,24 +17,11 @@ transposed graph is scheduled by graph.transpose with default_split_len = 256.
          than the forward fix-up's batch of 16, not a multiple of the backward
          fix-up's 8) + 2500 out of source 7 (10 chunks, the last one partial)
 
-Lane layouts: K = channels per lane, LH = lanes per head, as the two
-dispatchers choose for aligned contiguous inputs (mirrored and asserted on the
-CPU in tests/test_gatv2_ref_host.py):
-
-  (heads, C)   forward                               backward
-  (8,16)       8                                     2
-  (8,32)       8                                     4
-  (8,64)       8                                     8
-  (8,128)      16                                    16
-  (4,256)      16                                    16, LH 16
-  (2,64)       8                                     2, LH 32
-  (1,64)       8                                     1, LH 64
-  (3,12)       4, padding sub-lane and padding head  1
-  (5,24)       8                                     4, padding lanes and heads
-  (16,4)       4, LH 1                               1
-  (2,6)        fallback 2                            1
-  (3,6)        2, row stride not a multiple of 4     1
-  (2,7)        1                                     1
+Lane layouts: K = channels per lane, LH = lanes per head, as the two rules of
+csrc/kgx_attn_layout.h choose for aligned contiguous inputs.  The table of
+(heads, C) -> forward K, backward K, with what each pair is in the list for,
+is gatv2_ref.LAYOUTS; tests/test_attn_layout_host.py holds it, and the Python
+mirror of the rules, equal to the C++ on the CPU.
 
 Bounds, float64 reference throughout:
   out                     |got - ref| <= 1e-5 * max(1, |ref|)
