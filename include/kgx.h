@@ -651,6 +651,74 @@ int kgx_dot_attention_backward(const int32_t* rowptr, const int32_t* rows, int64
                                const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * kgx_dot_attention with edge features (PyG's TransformerConv with edge_dim):
+ * one projected edge row is added to the key in the score and to the value in
+ * the message.  For the row's CSR slots t (source j_t = col[t], edge row eps_t):
+ *   k'_t = k[j_t,h,:] + eps_t[h,:],  v'_t = v[j_t,h,:] + eps_t[h,:]
+ *                                              (one rounded fp32 add per element)
+ *   s_t = scale * sum_c q[i,h,c] * k'_t[c],  m, l as above (no epsilon)
+ *   out[i,h,:] = sum_t exp(s_t - m) / l * mask_t * v'_t
+ * e: the edge table [n_e, ld_e >= heads*channels], fp32, unit column stride.
+ * e_idx: the edge row of each CSR slot ([kept] int32); NULL: the slot itself
+ * (e is in CSR order).  A row outside [0, n_e) means the slot has no edge
+ * feature: its eps is zeros (the self-loop slots of a KGX_CSR_SELF_LOOPS graph,
+ * whose edge id is E + i, against a table of the E input edges).  Nothing is
+ * read out of range.  e == NULL (or n_e == 0) is kgx_dot_attention, which
+ * forwards here.  e joins the layout's alignment inputs (16-byte pointer and
+ * ld_e a multiple of 4 for the float4 layouts).  Everything else -- schedule,
+ * partials, stats, dropout, -inf / +inf / NaN per (row, head), empty rows, no
+ * atomics -- is kgx_dot_attention's.
+ * Errors, before any device work: as kgx_dot_attention (KGX_ERR_UNSUPPORTED
+ * for the same shapes); with e given, KGX_ERR_ARG for ld_e < heads*channels,
+ * ld_e >= 2^31, and n_e outside [0, 2^31).
+ * ------------------------------------------------------------------------- */
+int kgx_dot_attention_edge(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                           const int32_t* items, int64_t n_items,
+                           const int32_t* split, int64_t n_split,
+                           const int32_t* col, const float* q, int64_t ld_q, const float* k, int64_t ld_k,
+                           const float* v, int64_t ld_v,
+                           const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx,
+                           int heads, int channels, float scale,
+                           float* out, int64_t ld_out, float* partials, float* stats,
+                           const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Backward of kgx_dot_attention_edge.  As kgx_dot_attention_backward with k'
+ * and v' in the place of k[j] and v[j] (all three kernels form them by the
+ * same add, so s_t has the forward's bits), ds_t = p_t * (mask_t * <G_i,
+ * v'_t>_h - D[i,h]), and a fourth gradient:
+ *   grad_q[i]     = scale * sum_t ds_t * k'_t                 destination pass
+ *   grad_k[j], grad_v[j] as without edge features                  source pass
+ *   grad_e[eps_t] = scale * ds_t * q_i + p_t * mask_t * G_i   destination pass
+ * grad_e: [n_e, ld_ge >= heads*channels].  The destination pass stores the row
+ * of every slot that has an edge row (chunks of a split row store their own
+ * edges' rows; no partials): one writer per element when no two slots share an
+ * edge row.  Rows of no kept slot are not written -- the caller zeroes grad_e
+ * when the graph dropped input edges.  t_e_idx: the edge row of each
+ * TRANSPOSED slot (required with e; the source pass gathers eps_t beside q_i
+ * and G_i).  e and grad_e join the layout's alignment inputs.
+ * Errors, before any device work: as kgx_dot_attention_backward; with e given,
+ * KGX_ERR_ARG for grad_e or t_e_idx missing, ld_e or ld_ge < heads*channels or
+ * >= 2^31, and n_e outside [0, 2^31).
+ * ------------------------------------------------------------------------- */
+int kgx_dot_attention_edge_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                                    const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                                    const int32_t* col, const float* q, int64_t ld_q, const float* k, int64_t ld_k,
+                                    const float* v, int64_t ld_v,
+                                    const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx,
+                                    int heads, int channels, float scale,
+                                    const float* out, int64_t ld_out, const float* stats,
+                                    const float* grad_out, int64_t ld_grad,
+                                    const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+                                    const int32_t* t_items, int64_t t_n_items,
+                                    const int32_t* t_split, int64_t t_n_split,
+                                    const int32_t* t_col, const int32_t* t_key, const int32_t* t_e_idx,
+                                    float* grad_q, int64_t ld_gq, float* grad_k, int64_t ld_gk,
+                                    float* grad_v, int64_t ld_gv, float* grad_e, int64_t ld_ge,
+                                    float* dsum_ws, float* partials,
+                                    const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Fused segment softmax + weighted sum, the attention readouts' pooling (one
  * pass over x, online softmax; plus a fix-up for split segments):
  *   out[g,:] = sum_{i in g} softmax_g(s)_i * x[i,:]

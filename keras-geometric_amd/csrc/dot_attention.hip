@@ -11,6 +11,12 @@
 // gathered per edge (k_j and v_j), both unconditionally from clamped addresses,
 // masked on use.
 //
+// With an edge table (kgx_dot_attention_edge; PyG's edge_dim) a third row is
+// gathered per edge and added to both, k'_e = k[j_e] + eps_e and v'_e = v[j_e]
+// + eps_e, one rounded add per element, before any use; the kernels are
+// templated on that (EDGE), and the instantiations without it are the code of
+// the op without edge features.
+//
 // The score is bilinear, so both backward passes recompute p_e from q, k and
 // the saved (m, l): no E x H workspace, and no atomics -- every output element
 // has one writer and a fixed summation order, so a run gives the same bits
@@ -49,7 +55,33 @@ struct DotArgs {
   const int32_t* t_col;  // destination row of each transposed slot
   Drop t_drop;           // drop, keyed by the input edge id of each transposed slot
   AttnLayout lay;
+  // edge features (EDGE kernels only): table [n_e, ld_e], the edge row of each forward / transposed
+  // slot (e_idx null: the slot itself); a row outside [0, n_e) is a slot without a feature
+  const float* e;
+  int64_t ld_e;
+  int32_t n_e;
+  const int32_t* e_idx;
+  const int32_t* t_e_idx;
+  float* grad_e;  // backward: one row per kept slot's edge row, written by the destination pass
+  int64_t ld_ge;
 };
+
+// The edge row of slot t and whether it has one; the row to load from is clamped to 0 when it has none.
+__device__ __forceinline__ bool edge_row(const int32_t* idx, int32_t n_e, int32_t t, int32_t& r) {
+  r = idx ? idx[t] : t;
+  return uint32_t(r) < uint32_t(n_e);
+}
+
+// k' = k + eps, v' = v + eps (eps = 0 for a slot without an edge row): one rounded add each.
+template <int K>
+__device__ __forceinline__ void add_edge(float (&k)[K], float (&v)[K], const float (&e)[K], bool has) {
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    const float x = has ? e[c] : 0.0f;
+    k[c] += x;
+    v[c] += x;
+  }
+}
 
 // torch's softmax over a row's edges: no epsilon, so a row without edges is
 // written as zeros, and -inf scores (masked edges) weigh exactly 0.
@@ -71,7 +103,7 @@ struct DotSoftmax {
   }
 };
 
-template <int K, int U>
+template <int K, int U, bool EDGE>
 __global__ __launch_bounds__(kBlock) void dot_attention_kernel(DotArgs a) {
   const HeadLanes<K> L(a.lay, a.H, a.C);
   const int64_t ngroups = group_count(a.lay.lgG);
@@ -102,6 +134,18 @@ __global__ __launch_bounds__(kBlock) void dot_attention_kernel(DotArgs a) {
       for (int u = 0; u < U; ++u) {
         vload<K>(ks[u], a.k + row_off(j[u], a.ld_k) + L.f);
         vload<K>(vs[u], a.v + row_off(j[u], a.ld_v) + L.f);
+      }
+      if constexpr (EDGE) {  // the third row, loaded like the other two
+        float es[U][K];
+        bool he[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          he[u] = edge_row(a.e_idx, a.n_e, u < n ? e + u : end - 1, r);
+          vload<K>(es[u], a.e + row_off(he[u] ? r : 0, a.ld_e) + L.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) add_edge<K>(ks[u], vs[u], es[u], he[u]);
       }
       float s[U];
 #pragma unroll
@@ -135,13 +179,20 @@ __global__ __launch_bounds__(kBlock) void dot_attention_fixup_kernel(DotArgs a) 
 //   grad_v[j] = sum_{e: j_e = j} p_e mask_e G_i          source pass
 //   grad_k[j] = scale sum_{e: j_e = j} ds_e q_i          source pass
 // Both passes recompute s_e from q and k with the forward's operation order.
+// EDGE: k' and v' stand for k[j_e] and v[j_e] throughout, formed by the
+// forward's add, and the destination pass, which holds q_i and G_i and has
+// ds_e and p_e per edge, stores
+//   grad_e[eps_e] = scale ds_e q_i + p_e mask_e G_i
+// (chunks of a split row store their own edges' rows: no partials).  The
+// source pass gathers eps_e beside q_i and G_i.  The unroll stays the same:
+// no instantiation spills (DESIGN.md §12 has the registers).
 // ---------------------------------------------------------------------------
 template <int K>
 constexpr int bwd_unroll() {
   return K <= 4 ? 8 : (K == 8 ? 4 : 2);  // two K-wide rows per edge in flight: 64 registers
 }
 
-template <int K>
+template <int K, bool EDGE>
 __global__ __launch_bounds__(kBlock) void dot_attention_bwd_dst_kernel(DotArgs a) {
   constexpr int U = bwd_unroll<K>();
   const HeadLanes<K> L(a.lay, a.H, a.C);
@@ -175,6 +226,19 @@ __global__ __launch_bounds__(kBlock) void dot_attention_bwd_dst_kernel(DotArgs a
         vload<K>(ks[u], a.k + row_off(j, a.ld_k) + f);
         vload<K>(vs[u], a.v + row_off(j, a.ld_v) + f);
       }
+      int32_t er[U];  // EDGE: the slot's edge row, -1 without one
+      if constexpr (EDGE) {
+        float es[U][K];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          const bool he = edge_row(a.e_idx, a.n_e, e + u < end ? e + u : end - 1, r);
+          vload<K>(es[u], a.e + row_off(he ? r : 0, a.ld_e) + f);
+          er[u] = he ? r : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) add_edge<K>(ks[u], vs[u], es[u], er[u] >= 0);
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float ps = 0.0f, pa = 0.0f;
@@ -191,6 +255,15 @@ __global__ __launch_bounds__(kBlock) void dot_attention_bwd_dst_kernel(DotArgs a
           const float ds = p * (dmu * da - D);
 #pragma unroll
           for (int c = 0; c < K; ++c) gq[c] += ds * ks[u][c];
+          if constexpr (EDGE) {  // eps_e enters the score like k_j and the message like v_j: its one writer is here
+            if (valid && er[u] >= 0) {
+              const float sds = a.scale * ds, pm = p * dmu;
+              float ge[K];
+#pragma unroll
+              for (int c = 0; c < K; ++c) ge[c] = sds * qd[c] + pm * gr[c];
+              vstore<K>(a.grad_e + row_off(er[u], a.ld_ge) + f, ge);
+            }
+          }
         }
       }
     }
@@ -202,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void dot_attention_bwd_dst_kernel(DotArgs a
   }
 }
 
-template <int K>
+template <int K, bool EDGE>
 __global__ __launch_bounds__(kBlock) void dot_attention_bwd_src_kernel(DotArgs a) {
   constexpr int U = bwd_unroll<K>();
   const HeadLanes<K> L(a.lay, a.H, a.C);
@@ -233,13 +306,38 @@ __global__ __launch_bounds__(kBlock) void dot_attention_bwd_src_kernel(DotArgs a
         vload<K>(qi[u], a.q + row_off(i, a.ld_q) + f);
         vload<K>(gi[u], a.grad + row_off(i, a.ld_g) + f);
       }
+      float es[EDGE ? U : 1][K];  // EDGE: eps of each slot's edge, gathered beside q_i and G_i
+      bool he[U];
+      if constexpr (EDGE) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          he[u] = edge_row(a.t_e_idx, a.n_e, e + u < end ? e + u : end - 1, r);
+          vload<K>(es[u], a.e + row_off(he[u] ? r : 0, a.ld_e) + f);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float ps = 0.0f, pa = 0.0f;
+        if constexpr (EDGE) {
+          float ke[K], ve[K];
 #pragma unroll
-        for (int c = 0; c < K; ++c) {
-          ps += qi[u][c] * kj[c];
-          pa += gi[u][c] * vj[c];
+          for (int c = 0; c < K; ++c) {
+            ke[c] = kj[c];
+            ve[c] = vj[c];
+          }
+          add_edge<K>(ke, ve, es[u], he[u]);
+#pragma unroll
+          for (int c = 0; c < K; ++c) {
+            ps += qi[u][c] * ke[c];
+            pa += gi[u][c] * ve[c];
+          }
+        } else {
+#pragma unroll
+          for (int c = 0; c < K; ++c) {
+            ps += qi[u][c] * kj[c];
+            pa += gi[u][c] * vj[c];
+          }
         }
         const float s = a.scale * group_reduce(valid ? ps : 0.0f, a.lay.LH);
         const float da = group_reduce(valid ? pa : 0.0f, a.lay.LH);
@@ -275,26 +373,33 @@ __global__ __launch_bounds__(kBlock) void dot_attention_bwd_src_kernel(DotArgs a
 // at 4; K = 4: 1.38 / 1.51 / 1.47; K = 16: 1.55 / 1.53 / not run.  Two rows per
 // edge are already in flight, and 2 leaves K = 8 at 94 registers (5 waves per
 // SIMD against 4 at 3).  K <= 2 (float2 / scalar fallback) keeps 4 and was not
-// swept.  KGX_DOT_U overrides it for A/B runs (DESIGN.md §12 has the table).
-template <int K>
+// swept.  KGX_DOT_U overrides it for A/B runs (DESIGN.md §12 has the table),
+// except with an edge table at K = 16: three rows of 16 at U = 3 or 4 do not
+// fit 256 registers (the compiler parks 32 / 52 of them in AGPRs at one wave
+// per SIMD), so those two are not built.
+template <int K, bool EDGE>
 int launch_fwd(const DotArgs& a, hipStream_t s) {
-  static const int uf = env_int("KGX_DOT_U");
-  const int U = (uf >= 2 && uf <= 4) ? uf : (K <= 2 ? 4 : 2);
-  switch (U) {
-    case 2: return launch_with_fixup(dot_attention_kernel<K, 2>, dot_attention_fixup_kernel<K>, a, s);
-    case 3: return launch_with_fixup(dot_attention_kernel<K, 3>, dot_attention_fixup_kernel<K>, a, s);
-    default: return launch_with_fixup(dot_attention_kernel<K, 4>, dot_attention_fixup_kernel<K>, a, s);
+  if constexpr (EDGE && K == 16) {
+    return launch_with_fixup(dot_attention_kernel<K, 2, EDGE>, dot_attention_fixup_kernel<K>, a, s);
+  } else {
+    static const int uf = env_int("KGX_DOT_U");
+    const int U = (uf >= 2 && uf <= 4) ? uf : (K <= 2 ? 4 : 2);
+    switch (U) {
+      case 2: return launch_with_fixup(dot_attention_kernel<K, 2, EDGE>, dot_attention_fixup_kernel<K>, a, s);
+      case 3: return launch_with_fixup(dot_attention_kernel<K, 3, EDGE>, dot_attention_fixup_kernel<K>, a, s);
+      default: return launch_with_fixup(dot_attention_kernel<K, 4, EDGE>, dot_attention_fixup_kernel<K>, a, s);
+    }
   }
 }
 
 // The destination pass sums one row per slot (grad_q), the source pass two (grad_v | grad_k).
-template <int K>
+template <int K, bool EDGE>
 int launch_bwd(const DotArgs& a, hipStream_t s) {
   const int HC = a.H * a.C;
-  if (const int rc = launch_resident(dot_attention_bwd_dst_kernel<K>, a.sched.n_work(), a.lay.G, a, s)) return rc;
+  if (const int rc = launch_resident(dot_attention_bwd_dst_kernel<K, EDGE>, a.sched.n_work(), a.lay.G, a, s)) return rc;
   if (const int rc = launch_chunk_sum(a.sched, a.o.partials, a.o.ld_p, HC, HC, a.grad_q, a.ld_gq, a.grad_q, a.ld_gq, s))
     return rc;
-  if (const int rc = launch_resident(dot_attention_bwd_src_kernel<K>, a.t_sched.n_work(), a.lay.G, a, s)) return rc;
+  if (const int rc = launch_resident(dot_attention_bwd_src_kernel<K, EDGE>, a.t_sched.n_work(), a.lay.G, a, s)) return rc;
   return launch_chunk_sum(a.t_sched, a.o.partials, a.o.ld_p, HC, 2 * HC, a.grad_v, a.ld_gv, a.grad_k, a.ld_gk, s);
 }
 
@@ -303,18 +408,24 @@ int launch_bwd(const DotArgs& a, hipStream_t s) {
 
 using namespace kgx;
 
-extern "C" int kgx_dot_attention(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
-                                 int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
-                                 const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v,
-                                 int64_t ld_v, int heads, int channels, float scale, float* out, int64_t ld_out,
-                                 float* partials, float* stats, const int32_t* drop_key, float drop_p,
-                                 uint64_t drop_seed, kgx_stream_t stream_) {
+extern "C" int kgx_dot_attention_edge(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                                      const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                                      const int32_t* col, const float* q, int64_t ld_q, const float* k,
+                                      int64_t ld_k, const float* v, int64_t ld_v, const float* e, int64_t ld_e,
+                                      int64_t n_e, const int32_t* e_idx, int heads, int channels, float scale,
+                                      float* out, int64_t ld_out, float* partials, float* stats,
+                                      const int32_t* drop_key, float drop_p, uint64_t drop_seed,
+                                      kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
   KGX_REQUIRE(heads > 0 && channels > 0 && n_rows >= 0 && n_items >= 0 && n_split >= 0, KGX_ERR_ARG,
               "kgx_dot_attention: bad sizes");
-  if (n_rows == 0) return KGX_OK;
   const int64_t HC = int64_t(heads) * channels;
   const int64_t lim = int64_t(1) << 31;
+  KGX_REQUIRE(!e || (n_e >= 0 && n_e < lim), KGX_ERR_ARG, "kgx_dot_attention: edge table rows outside [0, 2^31)");
+  KGX_REQUIRE(!e || ld_e >= HC, KGX_ERR_ARG, "kgx_dot_attention: leading dimension of e < heads*channels");
+  KGX_REQUIRE(!e || ld_e < lim, KGX_ERR_ARG, "kgx_dot_attention: leading dimension of e >= 2^31");
+  if (n_rows == 0) return KGX_OK;
+  if (e && n_e == 0) e = nullptr;  // no row to read: every slot is without a feature
   KGX_REQUIRE(rowptr && rows && col && q && k && v && out, KGX_ERR_ARG, "kgx_dot_attention: null pointer");
   KGX_REQUIRE(ld_q >= HC && ld_k >= HC && ld_v >= HC && ld_out >= HC, KGX_ERR_ARG,
               "kgx_dot_attention: leading dimension < heads*channels");
@@ -323,7 +434,9 @@ extern "C" int kgx_dot_attention(const int32_t* rowptr, const int32_t* rows, int
   KGX_REQUIRE_DROP_P(drop_p, "kgx_dot_attention");
   KGX_REQUIRE(!items || n_split == 0 || (split && partials), KGX_ERR_ARG,
               "kgx_dot_attention: split rows need split list and partials");
-  const auto fits = [&](int b) { return attn_vec_ok(b, {q, k, v, out, partials}, {ld_q, ld_k, ld_v, ld_out}); };
+  const auto fits = [&](int b) {
+    return attn_vec_ok(b, {q, k, v, out, partials, e}, {ld_q, ld_k, ld_v, ld_out, e ? ld_e : 0});
+  };
   const bool vec4 = fits(16);
   int K = attn_pick_k(heads, channels, vec4, fits(8));
   KGX_REQUIRE(K > 0, KGX_ERR_UNSUPPORTED,
@@ -346,25 +459,52 @@ extern "C" int kgx_dot_attention(const int32_t* rowptr, const int32_t* rows, int
   a.o = {out, ld_out, partials, attn_partial_ld(heads, channels), stats, nullptr};
   a.drop = make_drop(drop_key, drop_p, drop_seed);
   a.lay = attn_layout(heads, channels, K);
-  return dispatch_k(K, [&](auto kk) { return launch_fwd<decltype(kk)::value>(a, stream); });
+  if (!e) return dispatch_k(K, [&](auto kk) { return launch_fwd<decltype(kk)::value, false>(a, stream); });
+  a.e = e;
+  a.ld_e = ld_e;
+  a.n_e = int32_t(n_e);
+  a.e_idx = e_idx;
+  return dispatch_k(K, [&](auto kk) { return launch_fwd<decltype(kk)::value, true>(a, stream); });
 }
 
-extern "C" int kgx_dot_attention_backward(
+extern "C" int kgx_dot_attention(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
+                                 int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
+                                 const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v,
+                                 int64_t ld_v, int heads, int channels, float scale, float* out, int64_t ld_out,
+                                 float* partials, float* stats, const int32_t* drop_key, float drop_p,
+                                 uint64_t drop_seed, kgx_stream_t stream_) {
+  return kgx_dot_attention_edge(rowptr, rows, n_rows, items, n_items, split, n_split, col, q, ld_q, k, ld_k, v, ld_v,
+                                nullptr, 0, 0, nullptr, heads, channels, scale, out, ld_out, partials, stats,
+                                drop_key, drop_p, drop_seed, stream_);
+}
+
+extern "C" int kgx_dot_attention_edge_backward(
     const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items, int64_t n_items,
     const int32_t* split, int64_t n_split, const int32_t* col, const float* q, int64_t ld_q, const float* k,
-    int64_t ld_k, const float* v, int64_t ld_v, int heads, int channels, float scale, const float* out,
-    int64_t ld_out, const float* stats, const float* grad_out, int64_t ld_grad, const int32_t* t_rowptr,
-    const int32_t* t_rows, int64_t n_src, const int32_t* t_items, int64_t t_n_items, const int32_t* t_split,
-    int64_t t_n_split, const int32_t* t_col, const int32_t* t_key, float* grad_q, int64_t ld_gq, float* grad_k,
-    int64_t ld_gk, float* grad_v, int64_t ld_gv, float* dsum_ws, float* partials, const int32_t* drop_key,
-    float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
+    int64_t ld_k, const float* v, int64_t ld_v, const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx,
+    int heads, int channels, float scale, const float* out, int64_t ld_out, const float* stats,
+    const float* grad_out, int64_t ld_grad, const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+    const int32_t* t_items, int64_t t_n_items, const int32_t* t_split, int64_t t_n_split, const int32_t* t_col,
+    const int32_t* t_key, const int32_t* t_e_idx, float* grad_q, int64_t ld_gq, float* grad_k, int64_t ld_gk,
+    float* grad_v, int64_t ld_gv, float* grad_e, int64_t ld_ge, float* dsum_ws, float* partials,
+    const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
   KGX_REQUIRE(heads > 0 && channels > 0 && n_rows >= 0 && n_src >= 0 && n_items >= 0 && n_split >= 0 &&
                   t_n_items >= 0 && t_n_split >= 0,
               KGX_ERR_ARG, "kgx_dot_attention_backward: bad sizes");
-  if (n_rows == 0 && n_src == 0) return KGX_OK;
   const int64_t HC = int64_t(heads) * channels;
   const int64_t lim = int64_t(1) << 31;
+  KGX_REQUIRE(!e || (n_e >= 0 && n_e < lim), KGX_ERR_ARG,
+              "kgx_dot_attention_backward: edge table rows outside [0, 2^31)");
+  KGX_REQUIRE(!e || (grad_e && t_e_idx), KGX_ERR_ARG,
+              "kgx_dot_attention_backward: an edge table needs grad_e and t_e_idx");
+  KGX_REQUIRE(!e || (ld_e >= HC && ld_ge >= HC), KGX_ERR_ARG,
+              "kgx_dot_attention_backward: leading dimension of e or grad_e < heads*channels");
+  KGX_REQUIRE(!e || (ld_e < lim && ld_ge < lim), KGX_ERR_ARG,
+              "kgx_dot_attention_backward: leading dimension of e or grad_e >= 2^31");
+  if (n_rows == 0 && n_src == 0) return KGX_OK;
+  if (e && n_e == 0) e = nullptr;  // no row to read or write
+  if (!e) grad_e = nullptr;
   KGX_REQUIRE(rowptr && rows && col && q && k && v && out && stats && grad_out && t_rowptr && t_rows && t_col &&
                   grad_q && grad_k && grad_v && dsum_ws,
               KGX_ERR_ARG, "kgx_dot_attention_backward: null pointer");
@@ -382,8 +522,8 @@ extern "C" int kgx_dot_attention_backward(
   KGX_REQUIRE(((!items || n_split == 0) && (!t_items || t_n_split == 0)) || partials, KGX_ERR_ARG,
               "kgx_dot_attention_backward: split rows need partials");
   const auto fits = [&](int b) {
-    return attn_vec_ok(b, {q, k, v, out, grad_out, grad_q, grad_k, grad_v, partials},
-                       {ld_q, ld_k, ld_v, ld_out, ld_grad, ld_gq, ld_gk, ld_gv, HC});
+    return attn_vec_ok(b, {q, k, v, out, grad_out, grad_q, grad_k, grad_v, partials, e, grad_e},
+                       {ld_q, ld_k, ld_v, ld_out, ld_grad, ld_gq, ld_gk, ld_gv, HC, e ? ld_e : 0, e ? ld_ge : 0});
   };
   const bool vec4 = fits(16);
   int K = attn_pick_k(heads, channels, vec4, fits(8));
@@ -420,5 +560,29 @@ extern "C" int kgx_dot_attention_backward(
   a.t_col = t_col;
   a.t_drop = make_drop(dropping ? t_key : nullptr, drop_p, drop_seed);
   a.lay = attn_layout(heads, channels, K);
-  return dispatch_k(K, [&](auto kk) { return launch_bwd<decltype(kk)::value>(a, stream); });
+  if (!e) return dispatch_k(K, [&](auto kk) { return launch_bwd<decltype(kk)::value, false>(a, stream); });
+  a.e = e;
+  a.ld_e = ld_e;
+  a.n_e = int32_t(n_e);
+  a.e_idx = e_idx;
+  a.t_e_idx = t_e_idx;
+  a.grad_e = grad_e;
+  a.ld_ge = ld_ge;
+  return dispatch_k(K, [&](auto kk) { return launch_bwd<decltype(kk)::value, true>(a, stream); });
+}
+
+extern "C" int kgx_dot_attention_backward(
+    const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items, int64_t n_items,
+    const int32_t* split, int64_t n_split, const int32_t* col, const float* q, int64_t ld_q, const float* k,
+    int64_t ld_k, const float* v, int64_t ld_v, int heads, int channels, float scale, const float* out,
+    int64_t ld_out, const float* stats, const float* grad_out, int64_t ld_grad, const int32_t* t_rowptr,
+    const int32_t* t_rows, int64_t n_src, const int32_t* t_items, int64_t t_n_items, const int32_t* t_split,
+    int64_t t_n_split, const int32_t* t_col, const int32_t* t_key, float* grad_q, int64_t ld_gq, float* grad_k,
+    int64_t ld_gk, float* grad_v, int64_t ld_gv, float* dsum_ws, float* partials, const int32_t* drop_key,
+    float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
+  return kgx_dot_attention_edge_backward(rowptr, rows, n_rows, items, n_items, split, n_split, col, q, ld_q, k, ld_k,
+                                         v, ld_v, nullptr, 0, 0, nullptr, heads, channels, scale, out, ld_out, stats,
+                                         grad_out, ld_grad, t_rowptr, t_rows, n_src, t_items, t_n_items, t_split,
+                                         t_n_split, t_col, t_key, nullptr, grad_q, ld_gq, grad_k, ld_gk, grad_v,
+                                         ld_gv, nullptr, 0, dsum_ws, partials, drop_key, drop_p, drop_seed, stream_);
 }

@@ -1,24 +1,29 @@
 """TransformerConv: dot-product (query / key / value) attention over edges.
 
 No reference counterpart (like PNAConv and DotProductDecoder); semantics are
-PyG's `TransformerConv` without edge features:
+PyG's `TransformerConv`, with edge features when `edge_dim` is set:
 
     q_i = lin_query(x_i),  k_j = lin_key(x_j),  v_j = lin_value(x_j)
-    alpha_e = softmax_i(<q_i, k_j>_h / sqrt(C))      per destination i and head h
-    out_i = sum_e dropout(alpha_e) v_j               heads concatenated or averaged
+    eps_e = lin_edge(edge_attr_e)                    edge_dim (no bias), else 0
+    alpha_e = softmax_i(<q_i, k_j + eps_e>_h / sqrt(C))   per destination i and head h
+    out_i = sum_e dropout(alpha_e) (v_j + eps_e)     heads concatenated or averaged
     r_i = lin_skip(x_i)                              root_weight
     out_i = beta_i r_i + (1 - beta_i) out_i,  beta_i = sigmoid(lin_beta([out_i, r_i, out_i - r_i]))   beta
     out_i = out_i + r_i                              root_weight without beta
 
 The scores, the segment softmax and the weighted sum are ONE fused kgx kernel
-(kgx_dot_attention): no E x H score or weight tensor exists, forward or
-backward.  key and value come from one kgx_dense launch with [W_k | W_v] when
+(kgx_dot_attention, kgx_dot_attention_edge with edge features): no E x H
+score or weight tensor exists, forward or backward.  The projected edge rows
+eps [E, heads * output_dim] (and their gradient) do exist; they are made in
+input-edge order and the kernel gathers them by edge id.  key and value come from one kgx_dense launch with [W_k | W_v] when
 2 * heads * output_dim <= KGX_DENSE_MAX_N; the kernel reads the two column
 halves in place.  No self loops are added (PyG adds none).
 
 inputs[0] may be a pair (x_i, x_j) of a bipartite graph, and inputs[1] a
 sampled Block (x then holds the block's n_src source rows, the output its
-first n_dst rows), as SAGEConv accepts it.
+first n_dst rows), as SAGEConv accepts it.  edge_attr [E, edge_dim] is a keyword
+or inputs[2], one row per edge of edge_index in its order; with a Block, one
+row per block edge: edge_attr_full[blk.edge_ids].
 """
 
 from __future__ import annotations
@@ -44,6 +49,7 @@ class TransformerConv(MessagePassing):
         beta: bool = False,
         dropout: float = 0.0,
         root_weight: bool = True,
+        edge_dim: int | None = None,
         use_bias: bool = True,
         kernel_initializer: str = "glorot_uniform",
         bias_initializer: str = "zeros",
@@ -58,6 +64,9 @@ class TransformerConv(MessagePassing):
         self.beta = bool(beta)
         self.dropout_rate = float(dropout)
         self.root_weight = bool(root_weight)
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+        if self.edge_dim is not None and self.edge_dim <= 0:
+            raise ValueError(f"TransformerConv: edge_dim must be positive, got {edge_dim}")
         self.use_bias = bool(use_bias)
         self.kernel_initializer = kernel_initializer
         self.bias_initializer = bias_initializer
@@ -66,6 +75,7 @@ class TransformerConv(MessagePassing):
         self.lin_value: Dense | None = None
         self.lin_skip: Dense | None = None
         self.lin_beta: Dense | None = None
+        self.lin_edge: Dense | None = None
 
     def _out_dim(self) -> int:
         return self.heads * self.output_dim if self.concat else self.output_dim
@@ -94,6 +104,8 @@ class TransformerConv(MessagePassing):
             self.lin_skip = self._dense(self._out_dim(), dst_shape[1], "lin_skip", self.use_bias)
             if self.beta:
                 self.lin_beta = self._dense(1, 3 * self._out_dim(), "lin_beta", False)
+        if self.edge_dim is not None:  # last: the weights of a layer without edge_dim keep their order
+            self.lin_edge = self._dense(hc, self.edge_dim, "lin_edge", False)
         self.built = True
 
     def forward(self, inputs, *args, **kwargs):
@@ -111,13 +123,28 @@ class TransformerConv(MessagePassing):
             node_shape = node_shape[0]
         return (node_shape[0] if node_shape else None, self._out_dim())
 
+    def _edge_rows(self, edge_attr, n_edges: int, device):
+        """edge_attr as fp32 [n_edges, edge_dim] on `device`; None for a layer without edge_dim."""
+        if self.edge_dim is None:
+            if edge_attr is not None:
+                raise NotImplementedError("TransformerConv: edge features (edge_attr) need a layer built with "
+                                          "edge_dim")
+            return None
+        if edge_attr is None:
+            raise ValueError(f"TransformerConv(edge_dim={self.edge_dim}) needs edge_attr [E, {self.edge_dim}]")
+        ea = to_device_tensor(edge_attr, torch.float32, device)
+        if ea.dim() != 2 or tuple(ea.shape) != (n_edges, self.edge_dim):
+            raise ValueError(f"TransformerConv: edge_attr must be [{n_edges}, {self.edge_dim}] (one row per edge), "
+                             f"got {tuple(ea.shape)}")
+        return ea
+
     def call(self, inputs, edge_attr=None, training=None):
-        if edge_attr is not None:
-            raise NotImplementedError("TransformerConv: edge features (edge_attr / edge_dim) are not supported")
         if not isinstance(inputs, (list, tuple)) or len(inputs) < 2:
             raise ValueError(f"Expected inputs to be [x, edge_index], got {inputs}")
         if len(inputs) > 2 and inputs[2] is not None:
-            raise NotImplementedError("TransformerConv: edge features (edge_attr / edge_dim) are not supported")
+            if edge_attr is not None:
+                raise ValueError("TransformerConv: edge_attr given both as inputs[2] and as a keyword")
+            edge_attr = inputs[2]
         x, edge_index = inputs[0], inputs[1]
         if isinstance(x, (list, tuple)):
             x_i = to_device_tensor(x[0], torch.float32)
@@ -134,12 +161,14 @@ class TransformerConv(MessagePassing):
             elif x_i.shape[0] != blk.n_dst:
                 raise ValueError(f"TransformerConv on a Block expects {blk.n_dst} destination rows, got "
                                  f"{x_i.shape[0]}")
-            return self._attend(x_i, x_j, blk.graph if blk.edge_index.shape[1] else None, training)
+            ea = self._edge_rows(edge_attr, blk.edge_index.shape[1], x_i.device)
+            return self._attend(x_i, x_j, blk.graph if blk.edge_index.shape[1] else None, training, ea)
         ei = edge_index_tensor(edge_index, x_i.device, allow_transpose=False)
+        ea = self._edge_rows(edge_attr, ei.shape[1], x_i.device)
         g = None
         if ei.shape[1] > 0 and x_i.shape[0] > 0:
             g = graph_for(edge_index, ei, x_j.shape[0], x_i.shape[0], n_features=self.heads * self.output_dim)
-        return self._attend(x_i, x_j, g, training)
+        return self._attend(x_i, x_j, g, training, ea)
 
     def _key_value(self, x_j):
         """(k, v): the two column halves of one kgx_dense with [W_k | W_v] when
@@ -153,7 +182,7 @@ class TransformerConv(MessagePassing):
             return kv[:, :hc], kv[:, hc:]
         return self.lin_key(x_j), self.lin_value(x_j)
 
-    def _attend(self, x_i, x_j, g, training):
+    def _attend(self, x_i, x_j, g, training, edge_attr=None):
         n, H, C = x_i.shape[0], self.heads, self.output_dim
         if n == 0:
             return torch.zeros((0, self._out_dim()), dtype=x_i.dtype, device=x_i.device)
@@ -163,9 +192,11 @@ class TransformerConv(MessagePassing):
             q = self.lin_query(x_i)
             k, v = self._key_value(x_j)
             drop = bool(training) and self.dropout_rate > 0
+            eps = None if edge_attr is None else self.lin_edge(edge_attr)
             out = kops.dot_attention(g, q, k, v, H, C, exact=self.exact,
                                      dropout=self.dropout_rate if drop else 0.0,
-                                     seed=int(torch.randint(0, 2**62, (1,)).item()) if drop else 0)
+                                     seed=int(torch.randint(0, 2**62, (1,)).item()) if drop else 0,
+                                     edge=eps, edge_order="input")
         if not self.concat:
             out = out.view(n, H, C).mean(dim=1)
         if self.root_weight:
@@ -194,6 +225,7 @@ class TransformerConv(MessagePassing):
                 "beta": self.beta,
                 "dropout": self.dropout_rate,
                 "root_weight": self.root_weight,
+                "edge_dim": self.edge_dim,
                 "use_bias": self.use_bias,
                 "kernel_initializer": self.kernel_initializer,
                 "bias_initializer": self.bias_initializer,

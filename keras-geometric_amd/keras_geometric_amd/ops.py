@@ -704,11 +704,26 @@ def _attn_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _edge_table(edge, edge_idx, HC, n_slots_csr):
+    """The edge table as the kernels read it: [n_e, heads*channels] in place; without
+    edge_idx its rows are the CSR slots."""
+    edge = _attn_table(edge, HC, "edge")
+    if edge_idx is None and edge.shape[0] != n_slots_csr:
+        raise ValueError(f"dot_attention: edge in CSR order must have {n_slots_csr} rows, got {edge.shape[0]}")
+    if edge_idx is not None and (edge_idx.dtype != torch.int32 or edge_idx.numel() != n_slots_csr):
+        raise ValueError(f"dot_attention: edge_idx must be int32 [{n_slots_csr}]")
+    return edge
+
+
 def _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, save_stats,
-                        drop_key=None, drop_p=0.0, drop_seed=0):
+                        drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     HC = heads * channels
     q, k, v = _attn_table(q, HC, "q"), _attn_table(k, HC, "k"), _attn_table(v, HC, "v")
-    dev = nat.require_device(q, k, v, rowptr, rows, col, items, split, drop_key)
+    if edge is not None:
+        edge = _edge_table(edge, edge_idx, HC, col.numel())
+    else:
+        edge_idx = None
+    dev = nat.require_device(q, k, v, rowptr, rows, col, items, split, drop_key, edge, edge_idx)
     n_dst = rowptr.numel() - 1
     if q.shape[0] != n_dst or k.shape[0] != v.shape[0]:
         raise ValueError(f"dot_attention: q has {q.shape[0]} rows for {n_dst} destinations, k {k.shape[0]} and v "
@@ -719,10 +734,12 @@ def _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channel
         return out, stats
     n_items, n_split = _sched_counts(items, split)
     partials = _attn_partials(dev, items, n_split, n_slots, heads, channels)
+    # no table: the entry point is kgx_dot_attention (which forwards to this one with these arguments)
+    e_args = (None, 0, 0, None) if edge is None else (nat.ptr(edge), _attn_ld(edge), edge.shape[0], nat.ptr(edge_idx))
     nat.check(
-        nat.lib().kgx_dot_attention(
+        nat.lib().kgx_dot_attention_edge(
             nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
-            nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), heads, channels,
+            nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), *e_args, heads, channels,
             float(scale), nat.ptr(out), out.stride(0), nat.ptr(partials), nat.ptr(stats) if save_stats else None,
             *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
         ),
@@ -748,15 +765,17 @@ def dot_attention_save(
     drop_key: Optional[torch.Tensor] = None,
     drop_p: float = 0.0,
     drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """kgx::dot_attention that also returns the per-row softmax statistics [n_dst, 2*heads]: (m, l)."""
     return _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, True,
-                               drop_key, drop_p, drop_seed)
+                               drop_key, drop_p, drop_seed, edge, edge_idx)
 
 
 @dot_attention_save.register_fake
 def _dot_attention_save_fake(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots,
-                             drop_key=None, drop_p=0.0, drop_seed=0):
+                             drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     n = rowptr.shape[0] - 1
     return q.new_empty((n, heads * channels)), q.new_empty((n, 2 * heads))
 
@@ -778,15 +797,19 @@ def dot_attention_op(
     drop_key: Optional[torch.Tensor] = None,
     drop_p: float = 0.0,
     drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
-    """out[i,h,:] = sum_e softmax_i(scale <q_i, k_j>_h)_e mask_e v[j_e,h,:] (kgx_dot_attention)."""
+    """out[i,h,:] = sum_e softmax_i(scale <q_i, k_j>_h)_e mask_e v[j_e,h,:] (kgx_dot_attention); with
+    `edge` [n_e, heads*channels], row edge_idx[slot] (None: the slot) is added to k_j and to v_j
+    (kgx_dot_attention_edge)."""
     return _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, False,
-                               drop_key, drop_p, drop_seed)[0]
+                               drop_key, drop_p, drop_seed, edge, edge_idx)[0]
 
 
 @dot_attention_op.register_fake
 def _dot_attention_fake(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, drop_key=None,
-                        drop_p=0.0, drop_seed=0):
+                        drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     return q.new_empty((rowptr.shape[0] - 1, heads * channels))
 
 
@@ -860,6 +883,105 @@ def _dot_attention_backward_fake(grad_out, q, k, v, out, stats, rowptr, rows, it
     hc = heads * channels
     return (q.new_empty((rowptr.shape[0] - 1, hc)), q.new_empty((t_rowptr.shape[0] - 1, hc)),
             q.new_empty((t_rowptr.shape[0] - 1, hc)))
+
+
+def dot_attention_edge_backward_into(grad_e, grad_out, q, k, v, edge, out, stats, rowptr, rows, items, split, col,
+                                     n_slots, t_rowptr, t_rows, t_items, t_split, t_col, t_key, t_slots, heads,
+                                     channels, scale, edge_idx, t_edge_idx, drop_key=None, drop_p=0.0, drop_seed=0):
+    """(grad_q, grad_k, grad_v) of kgx::dot_attention_save with an edge table, and
+    d edge written into the rows of `grad_e` [n_e, heads*channels] (a row view of
+    a wider tensor is written in place) that a kept slot names: the caller
+    zeroes it when the graph dropped input edges (kgx_dot_attention_edge_backward)."""
+    HC = heads * channels
+    q, k, v = _attn_table(q, HC, "q"), _attn_table(k, HC, "k"), _attn_table(v, HC, "v")
+    edge = _edge_table(edge, edge_idx, HC, col.numel())
+    if t_edge_idx.dtype != torch.int32 or t_edge_idx.numel() != t_col.numel():
+        raise ValueError(f"dot_attention: t_edge_idx must be int32 [{t_col.numel()}]")
+    if grad_e.dtype != torch.float32 or grad_e.shape != edge.shape or _attn_table(grad_e, HC, "grad_e") is not grad_e:
+        raise ValueError(f"dot_attention: grad_e must be fp32 {tuple(edge.shape)} with unit column stride, got "
+                         f"{grad_e.dtype} {tuple(grad_e.shape)} strides {grad_e.stride()}")
+    grad_out, out, stats = _f32c(grad_out), _f32c(out), _f32c(stats)
+    dev = nat.require_device(grad_out, q, k, v, edge, grad_e, out, stats, rowptr, rows, items, split, col, t_rowptr,
+                             t_rows, t_items, t_split, t_col, t_key, edge_idx, t_edge_idx, drop_key)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    g_q = torch.empty((n_dst, HC), dtype=torch.float32, device=dev)
+    g_k = torch.empty((n_src, HC), dtype=torch.float32, device=dev)
+    g_v = torch.empty((n_src, HC), dtype=torch.float32, device=dev)
+    if col.numel() == 0 or n_dst == 0 or n_src == 0:
+        return g_q.zero_(), g_k.zero_(), g_v.zero_()
+    dsum = torch.empty((n_dst, heads), dtype=torch.float32, device=dev)
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
+    partials = None
+    if (items is not None and n_split > 0) or (t_items is not None and t_n_split > 0):
+        partials = torch.empty((max(n_slots, t_slots, 1), 2 * HC), dtype=torch.float32, device=dev)
+    nat.check(
+        nat.lib().kgx_dot_attention_edge_backward(
+            nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
+            nat.ptr(q), _attn_ld(q), nat.ptr(k), _attn_ld(k), nat.ptr(v), _attn_ld(v), nat.ptr(edge),
+            _attn_ld(edge), edge.shape[0], nat.ptr(edge_idx), heads, channels, float(scale), nat.ptr(out),
+            out.stride(0), nat.ptr(stats), nat.ptr(grad_out), grad_out.stride(0),
+            nat.ptr(t_rowptr), nat.ptr(t_rows), n_src, nat.ptr(t_items), t_n_items, nat.ptr(t_split), t_n_split,
+            nat.ptr(t_col), nat.ptr(t_key), nat.ptr(t_edge_idx), nat.ptr(g_q), g_q.stride(0), nat.ptr(g_k),
+            g_k.stride(0), nat.ptr(g_v), g_v.stride(0), nat.ptr(grad_e), _attn_ld(grad_e), nat.ptr(dsum),
+            nat.ptr(partials), *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
+        ),
+        "kgx_dot_attention_edge_backward",
+    )
+    return g_q, g_k, g_v
+
+
+@torch.library.custom_op("kgx::dot_attention_edge_backward", mutates_args=())
+def dot_attention_edge_backward(
+    grad_out: torch.Tensor,
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    edge: torch.Tensor,
+    out: torch.Tensor,
+    stats: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_key: torch.Tensor,
+    t_slots: int,
+    heads: int,
+    channels: int,
+    scale: float,
+    edge_idx: Optional[torch.Tensor],
+    t_edge_idx: torch.Tensor,
+    zero_grad_edge: bool,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_q, grad_k, grad_v, grad_edge) of kgx::dot_attention_save with an edge
+    table; zero_grad_edge: some row of `edge` belongs to no kept slot."""
+    make = torch.zeros if zero_grad_edge or col.numel() == 0 else torch.empty
+    g_e = make((edge.shape[0], heads * channels), dtype=torch.float32, device=edge.device)
+    g_q, g_k, g_v = dot_attention_edge_backward_into(
+        g_e, grad_out, q, k, v, edge, out, stats, rowptr, rows, items, split, col, n_slots, t_rowptr, t_rows,
+        t_items, t_split, t_col, t_key, t_slots, heads, channels, scale, edge_idx, t_edge_idx, drop_key, drop_p,
+        drop_seed)
+    return g_q, g_k, g_v, g_e
+
+
+@dot_attention_edge_backward.register_fake
+def _dot_attention_edge_backward_fake(grad_out, q, k, v, edge, out, stats, rowptr, rows, items, split, col, n_slots,
+                                      t_rowptr, t_rows, t_items, t_split, t_col, t_key, t_slots, heads, channels,
+                                      scale, edge_idx, t_edge_idx, zero_grad_edge, drop_key=None, drop_p=0.0,
+                                      drop_seed=0):
+    hc = heads * channels
+    return (q.new_empty((rowptr.shape[0] - 1, hc)), q.new_empty((t_rowptr.shape[0] - 1, hc)),
+            q.new_empty((t_rowptr.shape[0] - 1, hc)), q.new_empty((edge.shape[0], hc)))
 
 
 @torch.library.custom_op("kgx::gather_rows", mutates_args=())
@@ -1495,6 +1617,15 @@ def aggregate_transform(
     return _aggregate_transform_raw(g, x, W, red, weighted, bias, pre_gin, gin_scale, exact, relu)
 
 
+def _fwd_slot32(t):
+    """int32 [kept] of a transposed graph: the forward CSR slot of each of its slots (cached on it)."""
+    slot = t.extras.get("fwd_slot32")
+    if slot is None:
+        slot = t.extras["fwd_slot"].to(torch.int32)
+        t.extras["fwd_slot32"] = slot
+    return slot
+
+
 def _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, drop_p=0.0, drop_seed=0):
     items, _, split, _, n_slots = g.work(exact)
     return _timed(lambda: torch.ops.kgx.gatv2(
@@ -1540,10 +1671,7 @@ class _GATv2Fn(torch.autograd.Function):
         alpha = torch.empty((max(g.kept, 1), H), dtype=torch.float32, device=dev)
         ds = torch.empty_like(alpha)
         partials = torch.empty((max(n_slots, t_slots, 1), H * C), dtype=torch.float32, device=dev)
-        slot = t.extras.get("fwd_slot32")
-        if slot is None:
-            slot = t.extras["fwd_slot"].to(torch.int32)
-            t.extras["fwd_slot32"] = slot
+        slot = _fwd_slot32(t)
         n_items, n_split = _sched_counts(items, split)
         t_n_items, t_n_split = _sched_counts(t_items, t_split)
         nat.check(
@@ -1583,48 +1711,62 @@ def gatv2_aggregate(
     return _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, float(dropout), int(seed))
 
 
-def _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, drop_p=0.0, drop_seed=0):
+def _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, drop_p=0.0, drop_seed=0, edge=None,
+                       edge_order="input"):
     items, _, split, _, n_slots = g.work(exact)
     return _timed(lambda: torch.ops.kgx.dot_attention(
         q, k, v, g.rowptr, g.rows, items, split, g.col, heads, channels, float(scale), n_slots,
         g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+        edge, g.eid if edge is not None and edge_order == "input" else None,
     ))
 
 
 class _DotAttentionFn(torch.autograd.Function):
     """Autograd of the fused dot-product attention: the forward keeps its
     output and per-row softmax statistics; kgx_dot_attention_backward runs a
-    destination pass (D, d q) over the forward CSR and a source pass (d k, d v)
-    over the transposed CSR, both recomputing the probabilities, hub rows split
-    into chunks, no atomics."""
+    destination pass (D, d q, and d edge with an edge table) over the forward
+    CSR and a source pass (d k, d v) over the transposed CSR, both recomputing
+    the probabilities, hub rows split into chunks, no atomics."""
 
     @staticmethod
-    def forward(ctx, q, k, v, g, heads, channels, scale, exact, drop_p, drop_seed):
+    def forward(ctx, q, k, v, edge, g, heads, channels, scale, exact, drop_p, drop_seed, edge_order):
         ctx.g, ctx.heads, ctx.channels, ctx.scale, ctx.exact = g, heads, channels, float(scale), exact
-        ctx.drop_p, ctx.drop_seed = drop_p, drop_seed
+        ctx.drop_p, ctx.drop_seed, ctx.edge_order = drop_p, drop_seed, edge_order
         items, _, split, _, n_slots = g.work(exact)
         out, stats = _timed(lambda: torch.ops.kgx.dot_attention_save(
             q, k, v, g.rowptr, g.rows, items, split, g.col, heads, channels, float(scale), n_slots,
             g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+            edge, g.eid if edge is not None and edge_order == "input" else None,
         ))
-        ctx.save_for_backward(q, k, v, out, stats)
+        ctx.has_edge = edge is not None
+        ctx.save_for_backward(q, k, v, out, stats, *((edge,) if ctx.has_edge else ()))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         from . import graph as G
 
-        q, k, v, out, stats = ctx.saved_tensors
+        q, k, v, out, stats = ctx.saved_tensors[:5]
         g = ctx.g
         t = G.transpose(g)
         items, _, split, _, n_slots = g.work(ctx.exact)
         t_items, _, t_split, _, t_slots = t.work(ctx.exact)
-        g_q, g_k, g_v = _timed(lambda: torch.ops.kgx.dot_attention_backward(
-            grad_out, q, k, v, out, stats, g.rowptr, g.rows, items, split, g.col, n_slots,
+        drop = (g.eid if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed))
+        if not ctx.has_edge:
+            g_q, g_k, g_v = _timed(lambda: torch.ops.kgx.dot_attention_backward(
+                grad_out, q, k, v, out, stats, g.rowptr, g.rows, items, split, g.col, n_slots,
+                t.rowptr, t.rows, t_items, t_split, t.col, t.eid, t_slots, ctx.heads, ctx.channels, ctx.scale, *drop,
+            ))
+            return g_q, g_k, g_v, None, None, None, None, None, None, None, None, None
+        by_input = ctx.edge_order == "input"
+        # input order: rows of edges the graph dropped, and none for its self-loop slots, stay zero
+        dropped = by_input and (g.kept != g.n_input_edges or bool(g.flags & nat.CSR_SELF_LOOPS))
+        g_q, g_k, g_v, g_e = _timed(lambda: torch.ops.kgx.dot_attention_edge_backward(
+            grad_out, q, k, v, ctx.saved_tensors[5], out, stats, g.rowptr, g.rows, items, split, g.col, n_slots,
             t.rowptr, t.rows, t_items, t_split, t.col, t.eid, t_slots, ctx.heads, ctx.channels, ctx.scale,
-            g.eid if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed),
+            g.eid if by_input else None, t.eid if by_input else _fwd_slot32(t), dropped, *drop,
         ))
-        return g_q, g_k, g_v, None, None, None, None, None, None, None
+        return g_q, g_k, g_v, g_e, None, None, None, None, None, None, None, None
 
 
 def dot_attention(
@@ -1639,19 +1781,35 @@ def dot_attention(
     exact: bool = False,
     dropout: float = 0.0,
     seed: int = 0,
+    edge: torch.Tensor | None = None,
+    edge_order: str = "input",
 ) -> torch.Tensor:
     """Fused dot-product graph attention (TransformerConv's message passing):
     out[i,h,:] = sum_{e: j_e -> i} softmax_i(scale <q_i, k_j>_h)_e v[j_e,h,:];
     q [n_dst, heads*channels], k and v [n_src, heads*channels] (row views of a
     wider tensor are read in place).  scale=None: 1/sqrt(channels).
     Differentiable in q, k and v.  dropout > 0: attention dropout of the
-    normalised weight per (edge, head), mask of (seed, input edge id, head)."""
+    normalised weight per (edge, head), mask of (seed, input edge id, head).
+
+    edge (PyG's edge_dim, already projected): one row per edge that is added to
+    k_j in the score and to v_j in the message; differentiable too.
+    edge_order="input": [g.n_input_edges, heads*channels] in input-edge order
+    (self-loop slots the graph added carry no feature); "csr": [g.kept,
+    heads*channels] in CSR slot order, which the kernel streams."""
     import math
 
     scale = 1.0 / math.sqrt(channels) if scale is None else float(scale)
-    if _needs_grad(q, k, v):
-        return _DotAttentionFn.apply(q, k, v, g, heads, channels, scale, exact, float(dropout), int(seed))
-    return _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, float(dropout), int(seed))
+    if edge is not None:
+        if edge_order not in ("input", "csr"):
+            raise ValueError(f"dot_attention: edge_order must be 'input' or 'csr', got {edge_order!r}")
+        rows = g.n_input_edges if edge_order == "input" else g.kept
+        if edge.dim() != 2 or edge.shape[0] != rows or edge.shape[1] != heads * channels:
+            raise ValueError(f"dot_attention: edge in {edge_order} order must be [{rows}, {heads * channels}], got "
+                             f"{tuple(edge.shape)}")
+    if _needs_grad(q, k, v, edge):
+        return _DotAttentionFn.apply(q, k, v, edge, g, heads, channels, scale, exact, float(dropout), int(seed),
+                                     edge_order)
+    return _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, float(dropout), int(seed), edge, edge_order)
 
 
 # ---------------------------------------------------------------------------
