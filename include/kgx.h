@@ -534,6 +534,15 @@ int kgx_spmm_max_backward(int reduce, int raw, const int32_t* rowptr, int64_t n_
                           const float* table, int64_t ld_table, int64_t F,
                           const float* grad_out, int64_t ld_grad_out,
                           float* grad_table, int64_t ld_grad_table, kgx_stream_t stream);
+/* The same with edge weights w[slot] (null: none), the backward of a weighted
+ * kgx_spmm / kgx_spmm_gemm MAX / MIN: the messages are the forward's fp32
+ * products table[idx[e]] * w[e] -- extreme and ties among them -- and
+ *   grad_table[idx[e], f] += (grad_out[i, f] / ties) * w[e].
+ * raw != 0 takes no weights (KGX_ERR_UNSUPPORTED). */
+int kgx_spmm_max_backward_w(int reduce, int raw, const int32_t* rowptr, int64_t n_rows, const int32_t* idx,
+                            const float* w, const float* table, int64_t ld_table, int64_t F,
+                            const float* grad_out, int64_t ld_grad_out,
+                            float* grad_table, int64_t ld_grad_table, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Fused GATv2 attention aggregation (single pass, online segment softmax).

@@ -141,6 +141,9 @@ _SIGNATURES = {
     "kgx_spmm_max_backward": [
         _int, _int, _i32p, _i64, _i32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, ctypes.c_void_p,
     ],
+    "kgx_spmm_max_backward_w": [
+        _int, _int, _i32p, _i64, _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, ctypes.c_void_p,
+    ],
     "kgx_gatv2_backward": [
         _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64, _i32p, _f32p, _f32p, _i64, _f32p, _int, _int,
         ctypes.c_float, _f32p, _i64, _f32p, _f32p, _f32p, _i64,

@@ -1083,7 +1083,8 @@ def _reduce_backward(g: CSRGraph, red: int, weighted: bool, by_edge: bool, table
     sum / mean: the transposed aggregation (graph.transpose: each source row
     gathers the gradient rows of its edges' destinations, in input-edge order);
     max / min: kgx_spmm_max_backward (ties share evenly, +-inf rows pass
-    nothing — torch scatter_reduce amax/amin under the reference's isinf guard);
+    nothing — torch scatter_reduce amax/amin under the reference's isinf guard;
+    weighted: extreme and ties among the products, each share times w_e);
     by_edge (message tensors): each message receives its row's gradient."""
     from . import graph as G
 
@@ -1114,10 +1115,14 @@ def _reduce_backward(g: CSRGraph, red: int, weighted: bool, by_edge: bool, table
         table = table.contiguous()
         gt = torch.zeros_like(table)
         idx = g.eid if by_edge else g.col
+        w = _f32c(g.w) if weighted else None  # the forward's messages were table[idx_e] * w_e
+        if weighted and (w is None or w.numel() != idx.numel()):
+            raise ValueError("graph was built without GCN normalisation weights")
         nat.check(
-            nat.lib().kgx_spmm_max_backward(
-                red, int(raw), nat.ptr(g.rowptr), g.n_dst, nat.ptr(idx), nat.ptr(table), table.stride(0), table.shape[1],
-                nat.ptr(grad_out), grad_out.stride(0), nat.ptr(gt), gt.stride(0), nat.stream(table.device),
+            nat.lib().kgx_spmm_max_backward_w(
+                red, int(raw), nat.ptr(g.rowptr), g.n_dst, nat.ptr(idx), nat.ptr(w), nat.ptr(table),
+                table.stride(0), table.shape[1], nat.ptr(grad_out), grad_out.stride(0), nat.ptr(gt), gt.stride(0),
+                nat.stream(table.device),
             ),
             "kgx_spmm_max_backward",
         )
@@ -1201,6 +1206,10 @@ def aggregate(
     if dropout and by_edge:
         raise ValueError("message dropout applies to gathered node rows, not to message tensors")
     if _needs_grad(table, bias, xroot):
+        if weighted and epilogue == nat.EPI_RAW and red in (nat.MAX, nat.MIN) and table.requires_grad:
+            # kgx_spmm_max_backward_w has no unguarded form: say so here, not in the middle of backward()
+            raise NotImplementedError("aggregate: a weighted max / min with the raw (unguarded) epilogue is "
+                                      "forward-only; differentiate the guarded form or drop the weights")
         return _AggregateFn.apply(table, bias, xroot, g, red, weighted, by_edge, epilogue, float(gin_scale), exact,
                                   float(dropout), int(seed))
     return _aggregate_raw(g, table, red, weighted, by_edge, epilogue, bias, xroot, gin_scale, exact, float(dropout),

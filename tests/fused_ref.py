@@ -27,8 +27,10 @@ RED = {"sum": 0, "mean": 1, "max": 2, "min": 3}
 
 
 def reference(g, x, W, red: str, weighted: bool, bias=None, pre_gin: bool = False, gin_scale: float = 1.0,
-              chunk_edges: int = 1 << 23):
-    """(y, scale): float64 [n, F_out] each."""
+              chunk_edges: int = 1 << 23, with_agg: bool = False):
+    """(y, scale): float64 [n, F_out] each; with_agg: (y, scale, a, aa), the
+    float64 [n, F] aggregate PRE(REDUCE(...)) the transform is applied to and
+    its |terms| twin as well (what the training forward keeps for dW)."""
     dev = x.device
     n, F = g.n_dst, x.shape[1]
     rowptr = g.rowptr.long()
@@ -37,6 +39,8 @@ def reference(g, x, W, red: str, weighted: bool, bias=None, pre_gin: bool = Fals
     W64 = W.double()
     y = torch.empty((n, W.shape[1]), dtype=torch.float64, device=dev)
     scale = torch.empty_like(y)
+    agg = torch.empty((n, F), dtype=torch.float64, device=dev) if with_agg else None
+    agg_abs = torch.empty_like(agg) if with_agg else None
     b64 = bias.double() if bias is not None else torch.zeros(W.shape[1], dtype=torch.float64, device=dev)
     r0 = 0
     while r0 < n:
@@ -69,8 +73,10 @@ def reference(g, x, W, red: str, weighted: bool, bias=None, pre_gin: bool = Fals
             aa = abs(gin_scale) * xr.abs() + aa
         y[r0:r1] = a @ W64 + b64
         scale[r0:r1] = aa @ W64.abs() + b64.abs()
+        if with_agg:
+            agg[r0:r1], agg_abs[r0:r1] = a, aa
         r0 = r1
-    return y, scale
+    return (y, scale, agg, agg_abs) if with_agg else (y, scale)
 
 
 def owners(g, rows: torch.Tensor) -> list:
@@ -86,20 +92,15 @@ def owners(g, rows: torch.Tensor) -> list:
     tiny = getattr(g, "_kgx_tiny", None)
     tiny_start = tiny[2] if tiny and tiny[0] is not None else n_items
     n_long = g.n_long if g.n_long >= 0 else n_items
-    out = []
-    for r in rows.tolist():
-        p = int(pos[r])
-        if p < 0:
-            out.append("none")
-        elif int(items[p, 3]) >= 0:
-            out.append("split")
-        elif p < n_long:
-            out.append("main")
-        elif p < tiny_start:
-            out.append("short")
-        else:
-            out.append("tiny")
-    return out
+    p = pos[rows.to(items.device).long()]
+    pc = p.clamp_min(0)
+    code = torch.full_like(p, 4)  # one readback for all rows
+    code[p < tiny_start] = 3
+    code[p < n_long] = 2
+    code[items[pc, 3] >= 0] = 1
+    code[p < 0] = 0
+    names = ("none", "split", "main", "short", "tiny")
+    return [names[c] for c in code.tolist()]
 
 
 def check(y, g, ref, label: str = "", tol: float = 1e-5) -> float:

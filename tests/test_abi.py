@@ -69,6 +69,10 @@ def test_argument_validation_without_device(lib):
     assert rc == 1 and b"dropout" in lib.kgx_last_error()
     # backward of max/min only; fused accumulate flag validation
     assert lib.kgx_spmm_max_backward(0, 0, None, 0, None, None, 0, 0, None, 0, None, 0, None) == 1
+    assert lib.kgx_spmm_max_backward_w(0, 0, None, 0, None, None, None, 0, 0, None, 0, None, 0, None) == 1
+    # the unguarded (raw) extreme has no weighted form
+    assert lib.kgx_spmm_max_backward_w(nat.MAX, 1, None, 0, None, ctypes.c_void_p(16), None, 0, 0, None, 0, None, 0,
+                                       None) == 4
     # rmat argument checks
     assert lib.kgx_rmat_edges(0, 4, 100, 1, 1, 1, 0, 10, None, None, None) == 1
 

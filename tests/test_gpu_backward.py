@@ -119,17 +119,67 @@ def test_weighted_sum_and_epilogue_backward(dev):
     assert_tol(xd2.grad, xr2.grad)
 
 
+@pytest.mark.parametrize("aggr", ["max", "min"])
+@pytest.mark.parametrize("split_len", [0, 32])
+def test_weighted_extreme_backward(dev, aggr, split_len):
+    """max / min of GCN-weighted messages x_j * w_e: the extreme and its ties are
+    taken among the products, and each winner's source receives its share times
+    w_e (kgx_spmm_max_backward_w).  Self loops and R-MAT's duplicate edges tie."""
+    N, F = 1200, 24
+    ei = _graph(N, 14000, seed=9)
+    x, gout = _x(N, F, 50), _x(N, F, 51)
+    g = G.build_csr(T(ei[0]).to(dev), T(ei[1]).to(dev), N, N, self_loops=True, gcn_norm=True, split_len=split_len)
+    xd = T(x).to(dev).requires_grad_(True)
+    y = kops.aggregate(g, xd, aggr, weighted=True, exact=split_len == 0)
+    y.backward(T(gout).to(dev))
+    xr = T(x).requires_grad_(True)
+    eil = R.add_self_loops(T(ei), N)
+    w = R.compute_gcn_normalization(eil, N)
+    yr = R.aggregate(aggr, xr[eil[0].long()] * w.unsqueeze(1), eil[1], N)
+    yr.backward(T(gout))
+    assert_tol(y, yr)
+    assert_tol(xd.grad, xr.grad)
+    # and the gradient is the weighted one, far from the unweighted selection's
+    xu = T(x).requires_grad_(True)
+    R.aggregate(aggr, xu[eil[0].long()], eil[1], N).backward(T(gout))
+    assert float((xu.grad - xr.grad).abs().max()) > 0.1
+
+
+def test_weighted_raw_extreme_is_forward_only(dev):
+    """The unguarded (EPI_RAW) max has no weighted backward: asking for its
+    gradient is refused at the call, before anything is launched; without
+    grad the forward runs."""
+    from keras_geometric_amd import _native as nat
+
+    N, F = 300, 8
+    ei = _graph(N, 2000, seed=52)
+    g = G.build_csr(T(ei[0]).to(dev), T(ei[1]).to(dev), N, N, self_loops=True, gcn_norm=True)
+    x = T(_x(N, F, 53)).to(dev)
+    y = kops.aggregate(g, x, "max", weighted=True, epilogue=nat.EPI_RAW, exact=True)
+    assert y.shape == (N, F)
+    with pytest.raises(NotImplementedError, match="forward-only"):
+        kops.aggregate(g, x.clone().requires_grad_(True), "max", weighted=True, epilogue=nat.EPI_RAW, exact=True)
+
+
 def _layer_grads(layer, x, ei, gout):
     y = layer([x, ei])
     y.backward(gout)
     return y, x.grad, [w.grad for w in layer.weights]
 
 
-@pytest.mark.parametrize("exact", [False, True])
-def test_gcn_layer_backward(dev, exact):
-    """Fused aggregate->transform (default) and GEMM+aggregate (exact) layers:
-    d/dx, d/dW, d/db vs autograd through the reference forward."""
-    N, Fi, Fo = 1500, 128, 64
+@pytest.mark.parametrize("exact,Fo", [pytest.param(False, 64, id="False"), pytest.param(True, 64, id="True"),
+                                      pytest.param(False, 128, id="fused128")])
+def test_gcn_layer_backward(dev, exact, Fo):
+    """d/dx, d/dW, d/db of GCNConv vs autograd through the reference forward.
+    Only `fused128` (128 -> 128) takes the fused aggregate->transform and its
+    training step (P kept by the forward, dx through the fused kernel on the
+    transposed graph, dW / db by kgx_gemm_tn): ops.fused_transform_supported
+    wants F_in <= F_out, so at 128 -> 64 both the default (`False`) and the
+    exact (`True`) layer run GEMM + aggregate (kgx_dense, then kgx_spmm).  The
+    fused parameter is held to the |terms|-scaled bound of
+    test_gcn_backward_flags, not to the sqrt(N) slack."""
+    N, Fi = 1500, 128
+    assert kops.fused_transform_supported(Fi, Fo) == (Fo == 128)
     ei = _graph(N, 18000, seed=11)
     x, gout = _x(N, Fi, 12), _x(N, Fo, 13)
     torch.manual_seed(0)  # weight init independent of the tests that ran before
@@ -144,6 +194,15 @@ def test_gcn_layer_backward(dev, exact):
     xr, Wr, br = T(x).requires_grad_(True), T(W).requires_grad_(True), T(b).requires_grad_(True)
     yr = R.gcn_forward(xr, T(ei), Wr, br)
     yr.backward(T(gout))
+    if Fo == 128:  # the fused step: error bound of a re-ordered fp32 sum, the same computation on |terms|
+        xa, Wa, ba = (T(np.abs(t)).requires_grad_(True) for t in (x, W, b))
+        ya = R.gcn_forward(xa, T(ei), Wa, ba)
+        ya.backward(T(np.abs(gout)))
+        assert_tol_scaled(y, yr, ya)
+        assert_tol_scaled(gx, xr.grad, xa.grad)
+        assert_tol_scaled(gW, Wr.grad, Wa.grad)
+        assert_tol_scaled(gb, br.grad, ba.grad)
+        return
     assert_tol(y, yr)
     assert_tol(gx, xr.grad)
     # dW sums over all N rows: relative to the magnitude of the sum's terms
@@ -179,13 +238,21 @@ def test_gin_layer_backward(dev, aggr, train_eps):
 
 
 @pytest.mark.parametrize("aggr", ["sum", "mean", "max"])
-@pytest.mark.parametrize("hidden", [[], [64]])
-def test_gin_fused_layer(dev, aggr, hidden):
-    """F_in = 128: (1+eps)x + aggr and the MLP's first Dense (bias, ReLU when
-    hidden) run in the fused kernel (bf16x3 MFMA).  Forward and d/dx, d/dW vs
-    autograd through the reference forward, within 1e-5 of the same
-    computation on |terms| (a bound on every intermediate's magnitude)."""
-    N, F, Fo = 1500, 128, 32
+@pytest.mark.parametrize("Fo,hidden", [pytest.param(32, [], id="hidden0"), pytest.param(32, [64], id="hidden1"),
+                                       pytest.param(128, [], id="fused128"), pytest.param(32, [128], id="fused-hidden128")])
+def test_gin_fused_layer(dev, aggr, Fo, hidden):
+    """F_in = 128.  In the `fused128` (128 -> 128) and `fused-hidden128`
+    (128 -> 128 -> 32) parameters (1+eps)x + aggr and the MLP's first Dense
+    (bias; ReLU when hidden, in the kernel's store without grad and outside it
+    with) run in the fused kernel (bf16x3 MFMA), and its training step keeps P
+    for dW.  `hidden0` (128 -> 32) and `hidden1` (128 -> 64 -> 32) exercise the
+    unfused MLP: ops.fused_transform_supported wants F_in <= the first Dense's
+    width, so there the layer aggregates with the GIN epilogue (kgx_spmm) and
+    runs kgx_dense.  Forward and d/dx, d/dW vs autograd through the reference
+    forward, within 1e-5 of the same computation on |terms| (a bound on every
+    intermediate's magnitude)."""
+    N, F = 1500, 128
+    assert kops.fused_transform_supported(F, (hidden + [Fo])[0]) == ((hidden + [Fo])[0] == 128)
     ei = _graph(N, 18000, seed=40)
     x, gout = _x(N, F, 41), _x(N, Fo, 42)
     torch.manual_seed(0)  # weight init independent of the tests that ran before
@@ -354,15 +421,22 @@ def test_backward_bipartite_wide_noncontiguous(dev, aggr):
     assert_tol(src_t.grad, xr.grad)
 
 
-@pytest.mark.parametrize("loops,norm", [(False, True), (True, False), (False, False)])
-def test_gcn_backward_flags(dev, loops, norm):
+@pytest.mark.parametrize("loops,norm,Fo", [
+    pytest.param(False, True, 64, id="False-True"), pytest.param(True, False, 64, id="True-False"),
+    pytest.param(False, False, 64, id="False-False"), pytest.param(False, True, 128, id="False-True-128"),
+    pytest.param(True, False, 128, id="True-False-128"), pytest.param(False, False, 128, id="False-False-128")])
+def test_gcn_backward_flags(dev, loops, norm, Fo):
+    """GCNConv without self loops and / or the normalisation.  The 128 -> 64
+    parameters run GEMM + aggregate (kgx_dense, kgx_spmm); the -128 ones the
+    fused aggregate->transform and its training step."""
     N, F = 500, 128
+    assert kops.fused_transform_supported(F, Fo) == (Fo == 128)
     ei = _graph(N, 4000, seed=32)
-    x, gout = _x(N, F, 33), _x(N, 64, 34)
+    x, gout = _x(N, F, 33), _x(N, Fo, 34)
     # without the symmetric normalisation (or with the 1e6 dinv of zero-in-degree
     # nodes when loops are off) the sums are large and cancel: bound-based check
     torch.manual_seed(0)  # weight init independent of the tests that ran before
-    layer = GCNConv(64, add_self_loops=loops, normalize=norm)
+    layer = GCNConv(Fo, add_self_loops=loops, normalize=norm)
     xd = T(x).to(dev).requires_grad_(True)
     layer([xd, T(ei).to(dev)])
     W, b = (t.detach().cpu() for t in layer.weights)
