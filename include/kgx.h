@@ -190,6 +190,59 @@ int kgx_schedule_build(const int32_t* rowptr, int64_t n_dst, int32_t split_len,
                        int64_t* info, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * kgx_work: one graph's work list -- the CSR, its degree-ordered schedule
+ * (kgx_schedule_build) and the packed degree <= 2 tail (tiny.py) -- as the
+ * argument structs of kgx_spmm_run ("spmm" below), kgx_spmm_gemm_run ("gemm")
+ * and kgx_spmm_gemm_f256_run ("f256") carry it.  Zero / NULL = absent.
+ *   rowptr, rows, n_rows   [all] CSR row pointer [n_rows + 1] and the row ids in
+ *       schedule order [n_rows].
+ *   items, n_items         [all] the (possibly split) item list of
+ *       kgx_schedule_build; split rows are finished by an in-call fix-up through
+ *       the call's `partials`.  items NULL: every row of `rows` is reduced whole
+ *       in CSR order and the schedule's other fields are not used (spmm: EXACT
+ *       mode).  KGX_STD ignores items (always EXACT, two sequential passes per row).
+ *   n_long_items           [all] where the degree-descending schedule's short
+ *       rows begin: items [n_long_items, n_short_end) are unsplit rows of degree
+ *       <= KGX_SHORT_ROW_MAX.
+ *       spmm: a second kernel takes them several per lane group (not with
+ *         message dropout or column slices wider than 64 lanes); must lie in
+ *         [0, n_items], n_items = none.  EXACT mode (items NULL): 0 <
+ *         n_long_items < n_rows names the same suffix of the degree-descending
+ *         `rows` list, rows[n_long_items, n_rows), for the same kernel (each row
+ *         still one chain of adds in CSR order: bit-identical); any other value
+ *         leaves every row to the main kernel.
+ *       gemm: the short-row kernel reduces them 64 rows per block iteration;
+ *         0 <= n_long_items <= n_short_end <= n_items, n_short_end = none.  With
+ *         a sliced schedule it is the kgx_slice_build call's n_long_items.
+ *       f256: items [0, n_short_end) go to the main kernel, as two launches when
+ *         0 <= n_long_items < n_short_end (the hub chunks and rows of degree >
+ *         KGX_SHORT_ROW_MAX first, then the short rows, gathered whole a tile
+ *         ahead); -1: one launch.
+ *   n_short_end            [gemm, f256] items [n_short_end, n_items), rows of
+ *       degree <= 2, are taken from tiny_pack instead of the item list.  tiny_pack
+ *       NULL, and always in spmm (no tiny-record path): must equal n_items.
+ *   tiny_pack, tiny_w      [gemm, f256; spmm: must be NULL] the packed tail,
+ *       built once per graph (tiny.py, kgx_tiny_pack): tiny_pack[n_items -
+ *       n_short_end][4] = {row, degree, col0, col1} (col1 = col0 for degree 1,
+ *       both any valid source for degree 0) and, when w is given, tiny_w[..][2]
+ *       = {w0, w1}.  Needs items.
+ *   n_tiny_deg2            [gemm] the first n_tiny_deg2 records have degree 2
+ *       (the rest <= 1: degree-descending order); in [0, n_items - n_short_end].
+ *   split, n_split         [all] {row, first_slot, n_chunks, degree} of the
+ *       split rows; n_split > 0 needs split and the call's partials.
+ *   idx, w                 [all] per CSR slot the gathered row (col, or eid for
+ *       a per-edge message tensor) and, optional, the edge weight.
+ * ------------------------------------------------------------------------- */
+enum { KGX_SHORT_ROW_MAX = 7 };
+typedef struct kgx_work {
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items;  int64_t n_items; int64_t n_long_items; int64_t n_short_end;
+  const int32_t* tiny_pack; const float* tiny_w; int64_t n_tiny_deg2;
+  const int32_t* split;  int64_t n_split;
+  const int32_t* idx;    const float* w;
+} kgx_work;
+
+/* ---------------------------------------------------------------------------
  * Fused gather -> (weight) -> segment reduction -> epilogue, one launch.
  *   out[row, f] = EPI( REDUCE_{e in CSR row} table[idx[e], f] * (w ? w[e] : 1) )
  *
@@ -201,15 +254,53 @@ int kgx_schedule_build(const int32_t* rowptr, int64_t n_dst, int32_t split_len,
  * With idx = col and table = node features it is the node-gather SpMM; with
  *   idx = eid and table = a per-edge message tensor [E,F] it is the reference's
  *   Aggregator.aggregate(messages, target_idx, dim_size) on arbitrary messages.
- * Work list: if items != NULL the (possibly split) item list of
- *   kgx_schedule_build is used and split rows are finished by an in-call fix-up
- *   (partials: n_slots*F floats); otherwise every row of `rows` is reduced
- *   sequentially in CSR order (EXACT: bit-identical to the reference's
- *   sequential scatter_add / scatter_reduce for identical messages).
- * KGX_STD ignores items (always EXACT, two sequential passes per row).
- * drop_key (optional, SUM only): per-slot keys of the message dropout mask
- * (see kgx_dropout_mask); the message is (table[idx] * mask) * w.
+ *
+ * kgx_spmm_run takes its arguments as a kgx_spmm_args (zero-fill it, then set
+ * the fields the launch needs):
+ *   struct_size   sizeof(kgx_spmm_args), else KGX_ERR_ARG (a binding of another header).
+ *   reduce, epilogue   a kgx_reduce and a kgx_epilogue.  EPI_BIAS needs bias,
+ *       EPI_GIN xroot with ld_x >= F, EPI_ACCUM reduce KGX_SUM.
+ *   work          the work list (kgx_work; no tiny records).  items NULL is EXACT
+ *       mode: each row one sequential reduction in CSR order, bit-identical to the
+ *       reference's sequential scatter_add / scatter_reduce for identical messages.
+ *   table, ld_table, F   the gathered table [*, ld_table >= F], ld_table < 2^31.
+ *   table2, n_table1   gather from TWO tables: sources c < n_table1 are rows of
+ *       table, c >= n_table1 rows c - n_table1 of table2 (same ld_table); 0 <=
+ *       n_table1 < 2^31.  Needs the schedule (items; not EXACT / std), plain or
+ *       weighted KGX_SUM, no dropout.  The sharded GIN / SAGE layers reduce a
+ *       row's own-source and halo edges in one pass (distributed.py;
+ *       gin_conv.py:216-222, sage_conv.py:300-348).  table2 NULL: one table.
+ *   out, ld_out   [n_rows, ld_out >= F].
+ *   bias, xroot, ld_x, gin_scale   the epilogues' operands (kgx_epilogue).
+ *   drop_key, drop_p, drop_seed   (optional, SUM only, 0 <= p < 1) per-slot keys
+ *       of the message dropout mask (see kgx_dropout_mask); the message is
+ *       (table[idx] * mask) * w.
+ *   partials      n_slots * F floats, needed when the schedule has split rows.
+ *   counters      EXACT mode only (ignored with items): two caller-owned int32,
+ *       zeroed before the call, from which the hub-row kernel (rows of >= 2048
+ *       edges) hands out its (row, column group) items dynamically, so its
+ *       blocks balance instead of waiting behind the largest row (bit-identical
+ *       results: every row is still reduced by one lane chain in CSR order,
+ *       aggregators.py:126-137).  NULL: the static schedule.  With counters the
+ *       hub kernel also forks onto a library-owned stream beside the main
+ *       kernel (joined back into `stream` before the call returns), and the
+ *       main kernel takes interleaved batches of rows from counters[1] (batch b
+ *       = rows b, b + NB, ..., one atomic per 8 rows), so the GPU is not idle
+ *       behind the largest hub row (KGX_EXACT_FORK=0: the sequential form).
+ * kgx_spmm is the minimal positional form: kgx_spmm_run with n_long_items =
+ * n_short_end = n_items, one table and no counters.
  * ------------------------------------------------------------------------- */
+typedef struct kgx_spmm_args {
+  uint64_t struct_size;
+  int32_t reduce, epilogue;
+  kgx_work work;
+  const float* table; int64_t ld_table; const float* table2; int64_t n_table1; int64_t F;
+  float* out; int64_t ld_out;
+  const float* bias; const float* xroot; int64_t ld_x; float gin_scale; float drop_p;
+  const int32_t* drop_key; uint64_t drop_seed;
+  float* partials; int32_t* counters;
+} kgx_spmm_args;
+int kgx_spmm_run(const kgx_spmm_args* a, kgx_stream_t stream);
 int kgx_spmm(int reduce, int epilogue,
              const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
              const int32_t* items, int64_t n_items,
@@ -220,43 +311,6 @@ int kgx_spmm(int reduce, int epilogue,
              const float* bias, const float* xroot, int64_t ld_x, float gin_scale,
              const int32_t* drop_key, float drop_p, uint64_t drop_seed,
              float* partials, kgx_stream_t stream);
-/* kgx_spmm with the schedule's short-row suffix named: items [n_long_items,
- * n_items) are unsplit rows of degree <= KGX_SHORT_ROW_MAX (defined below),
- * taken several per lane group by a second kernel (not with message dropout
- * or column slices wider than 64 lanes).  n_long_items = n_items is kgx_spmm.
- * EXACT mode (items = NULL): 0 < n_long_items < n_rows names the same suffix
- * of the degree-descending `rows` list, rows[n_long_items, n_rows), for the
- * same kernel (each row still one chain of adds in CSR order: bit-identical);
- * any other value leaves every row to the main kernel. */
-int kgx_spmm_ex(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split,
-                int64_t n_split, const int32_t* idx, const float* w, const float* table, int64_t ld_table,
-                int64_t F, float* out, int64_t ld_out, const float* bias, const float* xroot, int64_t ld_x,
-                float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed, float* partials,
-                kgx_stream_t stream);
-
-/* kgx_spmm_ex2: kgx_spmm_ex gathering from TWO tables: sources c < n_table1 are
- * rows of table, c >= n_table1 rows c - n_table1 of table2 (same ld_table).
- * Needs the schedule (items; not EXACT / std).  The sharded GIN / SAGE layers
- * reduce a row's own-source and halo edges in one pass (distributed.py).
- * table2 NULL: kgx_spmm_ex.
- * counters (EXACT mode, items NULL): two caller-owned int32, zeroed before the
- * call, from which the hub-row kernel (rows of >= 2048 edges) hands out its
- * (row, column group) items dynamically, so its blocks balance instead of
- * waiting behind the largest row (bit-identical results: every row is still
- * reduced by one lane chain in CSR order, aggregators.py:126-137).  NULL: the
- * static schedule.  With counters the hub kernel also forks onto a
- * library-owned stream beside the main kernel (joined back into `stream`
- * before the call returns), and the main kernel takes interleaved batches of
- * rows from counters[1] (batch b = rows b, b + NB, ..., one atomic per 8 rows),
- * so the GPU is not idle behind the largest hub row (KGX_EXACT_FORK=0: the
- * sequential form). */
-int kgx_spmm_ex2(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                 const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split, int64_t n_split,
-                 const int32_t* idx, const float* w, const float* table, int64_t ld_table, const float* table2,
-                 int64_t n_table1, int64_t F, float* out, int64_t ld_out, const float* bias, const float* xroot,
-                 int64_t ld_x, float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed,
-                 float* partials, int32_t* counters, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Fused multi-aggregation: several reducers of one neighbourhood from ONE
@@ -321,27 +375,29 @@ int kgx_dropout_mask(uint64_t seed, float p, const int32_t* keys, int64_t n, int
  * algebraically equal aggregate-then-transform order (W applied once per row
  * on MFMA as the six significant products of a three-way bf16 split of both
  * operands: f32-accurate); tolerance-equal to the reference, not bit-equal.
- * Shapes: F_in and F_out multiples of 4 <= 128, W [F_in, F_out] row-major.
- * reduce in {SUM, MEAN, MAX, MIN}; partials: n_slots * 128 floats.
- * agg_out (optional, [n, ld_agg >= F_in]): also store PRE(REDUCE(...)), the
- * rows before the transform — what the backward's dW = agg^T dOut needs.
+ * Two calls take one kgx_fused_args (below): kgx_spmm_gemm_run for F_in <= 128
+ * and kgx_spmm_gemm_f256_run for 256-wide rows -- GINConv's (1+eps) x + aggr ->
+ * Dense at BASELINE config C4 (gin_conv.py:216-225, 129-162) and GCNConv 256 ->
+ * 256 (gcn_conv.py:233-272) without the [N, 256] aggregate written and read back.
+ * kgx_spmm_gemm is the minimal positional form of kgx_spmm_gemm_run.
  * ------------------------------------------------------------------------- */
 /* KGX_FUSED_SHARE_GPU: launch (den - 1) / den of the resident grid (den =
  * KGX_SHARE_DEN, default 16; the 256-wide kernels take the flag and ignore it), leaving block slots
  * for kernels of a concurrent stream (the sharded layer's RCCL exchange).
  * KGX_FUSED_RELU: out = max(bias + ..., 0), the activation of a GIN MLP's
  * first Dense (gin_conv.py:129-162) or SAGEConv's activation; with ACCUMULATE
- * it applies to the sum (out = max(out + ..., 0)).  kgx_spmm_gemm_f256 rejects
- * RELU | ACCUMULATE. */
+ * it applies to the sum (out = max(out + ..., 0)).  kgx_spmm_gemm_f256_run
+ * rejects RELU | ACCUMULATE. */
 /* KGX_FUSED_CU_SPLIT: run the schedule's tail launches on a CU-masked stream
  * over 8 of every 32 CUs, beside the main launches on the other CUs; both
  * streams are forked from and joined back into `stream` (before the hub
  * fix-up).  Outputs are bit-identical to the one-stream order.
- * kgx_spmm_gemm_f256 / _f256_ex: the tail is the degree <= 2 records (MFMA-
- * bound), the main part the long rows and degree 3..7 (memory-bound);
+ * kgx_spmm_gemm_f256_run: the tail is the degree <= 2 records (MFMA-bound),
+ * the main part the long rows and degree 3..7 (memory-bound);
  * KGX_F256_CU_SPLIT (environment) = tail CUs per 32, 0 = ignore the flag.
- * kgx_spmm_gemm*: the tail is the short-row and tiny-record launches, the main
- * part spmm_gemm_kernel; KGX_FUSED_CU_SPLIT (environment) = tail CUs per 32. */
+ * kgx_spmm_gemm, kgx_spmm_gemm_run: the tail is the short-row and tiny-record
+ * launches, the main part spmm_gemm_kernel; KGX_FUSED_CU_SPLIT (environment) =
+ * tail CUs per 32. */
 enum { KGX_FUSED_PRE_GIN = 1, KGX_FUSED_ACCUMULATE = 2, KGX_FUSED_SHARE_GPU = 4, KGX_FUSED_RELU = 8,
        KGX_FUSED_CU_SPLIT = 16 };
 int kgx_spmm_gemm(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
@@ -350,53 +406,8 @@ int kgx_spmm_gemm(int reduce, const int32_t* rowptr, const int32_t* rows, int64_
                   const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
                   float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
                   kgx_stream_t stream);
-/* kgx_spmm_gemm with the schedule's short-row suffix named: items
- * [n_long_items, n_items) are rows of degree <= KGX_SHORT_ROW_MAX (the degree-ordered
- * schedule's tail, never split), reduced 64 rows per block iteration by a
- * second kernel.  n_long_items = n_items is kgx_spmm_gemm. */
-enum { KGX_SHORT_ROW_MAX = 7 };
-int kgx_spmm_gemm_ex(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                     const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split,
-                     int64_t n_split, const int32_t* idx, const float* w, const float* x, int64_t ld_x,
-                     int64_t F_in, const float* W, int64_t F_out, const float* bias, int flags,
-                     float gin_scale, float* out, int64_t ld_out, float* partials, float* agg_out,
-                     int64_t ld_agg, kgx_stream_t stream);
 
-/* kgx_spmm_gemm_ex2: kgx_spmm_gemm_ex with the schedule's tail of rows of degree
- * <= 2 ([n_short_end, n_items)) taken from packed records instead of the item
- * list: tiny_pack[n_items - n_short_end][4] = {row, degree, col0, col1} (col1 =
- * col0 for degree 1, both any valid source for degree 0) and, when w is given,
- * tiny_w[..][2] = {w0, w1}; the first n_tiny_deg2 records have degree 2 (the
- * rest <= 1: degree-descending order).  Built once per graph (tiny.py).  Items
- * [n_long_items, n_short_end) go to the short-row kernel as before.  tiny_pack
- * NULL: n_short_end must equal n_items.  Same boundary as kgx_spmm_gemm
- * (gcn_conv.py:233-272, aggregators.py:56-167). */
-int kgx_spmm_gemm_ex2(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                      const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                      const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                      const int32_t* split, int64_t n_split,
-                      const int32_t* idx, const float* w, const float* x, int64_t ld_x, int64_t F_in,
-                      const float* W, int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
-                      int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg, kgx_stream_t stream);
-
-/* kgx_spmm_gemm_ex3: kgx_spmm_gemm_ex2 gathering from TWO feature tables:
- * source columns c < n_x1 are rows of x, columns c >= n_x1 are rows
- * c - n_x1 of x2 (same leading dimension ld_x, 16-byte aligned).  The sharded
- * layers' halo pass reads a row's own-source edges from the layer input and
- * its halo edges from the exchange's receive buffer in ONE pass, so the row is
- * written once instead of written and read-modify-written (distributed.py;
- * gcn_conv.py:233-272, gin_conv.py:216-225 per shard).  With x2: sums only
- * (weighted or not, GIN's pre-scale allowed), F_in 128, F_out % 16 == 0.
- * x2 NULL: kgx_spmm_gemm_ex2.  Rows indexed by pre_gin are rows of x. */
-int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                      const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                      const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                      const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
-                      const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
-                      const float* W, int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
-                      int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg, kgx_stream_t stream);
-
-/* Sliced schedule of the fused launch (kgx_spmm_gemm_ex4): rows of degree >= T
+/* Sliced schedule of the fused launch (kgx_fused_args.slice): rows of degree >= T
  * (the split hub rows among them; T <= split_len) have their edges regrouped by
  * SOURCE CLASS, a hash of the source id into [0, C): kgx_slice_class below.
  * Each XCD's L2 then holds one class of the hot source rows instead of a copy
@@ -435,67 +446,75 @@ int kgx_slice_build(const int32_t* rowptr, const int32_t* col, const float* w, c
                     int32_t* items_s, int64_t cap_items, int32_t* lists, int32_t* fix, void* workspace,
                     size_t workspace_bytes, int64_t* info, kgx_stream_t stream);
 
-/* kgx_spmm_gemm_ex4: kgx_spmm_gemm_ex3 with a sliced schedule (kgx_slice_build)
- * for the main kernel: n_classes lists (4 or 8), block b of the main kernel on
- * list b % n_classes -- an XCD affinity label only: every item is reduced once
- * by a statically determined block, and results do not depend on where blocks
- * run.  sl_tiles = ceil(longest list / 16).  The sliced rows' chunks write
- * partials (n_slots of kgx_slice_build * 128 floats; `partials` must hold the
- * larger of the two schedules' slots) and sl_split / sl_n_split (the `fix`
- * records) replace split / n_split; n_long_items is the kgx_slice_build
- * call's.  head_short_end (<= n_short_end; anything <= n_long_items: none):
- * under KGX_FUSED_CU_SPLIT the short-row items [n_long_items, head_short_end)
- * run on the head's CUs behind the main kernel, by the short-row kernel, and
- * the tail's CUs take the rest -- the knob that rebalances the two legs once
- * slicing has shortened the head.  Unweighted or weighted sums, one
- * table, F_in 128, F_out % 16 == 0.  When no multiple of n_classes blocks fits
- * the launch, it runs unsliced from items / split as kgx_spmm_gemm_ex3 does.
- * n_classes 0: kgx_spmm_gemm_ex3.  Rows that are not sliced get bit-identical
- * results either way. */
-int kgx_spmm_gemm_ex4(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                      const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                      const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                      const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
-                      const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
-                      const float* W, int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
-                      int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                      const int32_t* sl_items, const int32_t* sl_lists, int n_classes, int64_t sl_tiles,
-                      const int32_t* sl_idx, const float* sl_w, const int32_t* sl_split, int64_t sl_n_split,
-                      int64_t head_short_end, kgx_stream_t stream);
+/* kgx_slice: a sliced schedule (kgx_slice_build) for kgx_spmm_gemm_run's main
+ * kernel.  kgx_spmm_gemm_f256_run has none: n_classes must be 0 there.
+ *   n_classes     0 = unsliced, nothing else is read; else 4 or 8 lists, block b
+ *       of the main kernel on list b % n_classes -- an XCD affinity label only:
+ *       every item is reduced once by a statically determined block, and
+ *       results do not depend on where blocks run.  Rows that are not sliced
+ *       get bit-identical results either way.  Needs work.items and partials;
+ *       unweighted or weighted sums, one table, F_in 128, F_out % 16 == 0
+ *       (anything else: KGX_ERR_UNSUPPORTED).  When no multiple of n_classes
+ *       blocks fits the launch (kgx_slice_grid), it runs unsliced from
+ *       work.items / work.split.
+ *   items, lists  kgx_slice_build's items_s and lists.
+ *   tiles         ceil(longest list / 16), > 0.
+ *   idx, w        col_s / w_s, the sliced rows' regrouped edges (w needed with work.w).
+ *   split, n_split   the `fix` records, n_split > 0; they replace work.split /
+ *       work.n_split.  The sliced rows' chunks write partials: n_slots of
+ *       kgx_slice_build * 128 floats, and `partials` must hold the larger of
+ *       the two schedules' slots.
+ *   head_short_end   (<= work.n_short_end; anything <= work.n_long_items: none)
+ *       under KGX_FUSED_CU_SPLIT the short-row items [n_long_items,
+ *       head_short_end) run on the head's CUs behind the main kernel, by the
+ *       short-row kernel, and the tail's CUs take the rest -- the knob that
+ *       rebalances the two legs once slicing has shortened the head. */
+typedef struct kgx_slice {
+  const int32_t* items; const int32_t* lists; int64_t n_classes; int64_t tiles;
+  const int32_t* idx; const float* w; const int32_t* split; int64_t n_split;
+  int64_t head_short_end;
+} kgx_slice;
 
-/* kgx_spmm_gemm_f256: kgx_spmm_gemm for 256-wide rows (F_in == 256, F_out a
- * multiple of 16 <= 256; partials n_slots * 256 floats).  GINConv's
- * (1+eps) x + aggr -> Dense at BASELINE config C4 (gin_conv.py:216-225,
- * 129-162) and GCNConv 256 -> 256 (gcn_conv.py:233-272) without the [N, 256]
- * aggregate written and read back.  Items [0, n_short_end) go to the main
- * kernel (as two launches when 0 <= n_long_items < n_short_end: the hub chunks
- * and rows of degree > KGX_SHORT_ROW_MAX first, then the rows of degree <=
- * KGX_SHORT_ROW_MAX, gathered whole a tile ahead; -1: one launch); with tiny_pack, the schedule's tail [n_short_end, n_items) of rows of
- * degree <= 2 comes from the packed records of kgx_spmm_gemm_ex2 (tiny_pack
- * NULL: n_short_end must equal n_items).  One feature table; same flags,
- * argument meaning and error behaviour as kgx_spmm_gemm. */
-int kgx_spmm_gemm_f256(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                       const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                       const int32_t* tiny_pack, const float* tiny_w, const int32_t* split, int64_t n_split,
-                       const int32_t* idx, const float* w, const float* x, int64_t ld_x, int64_t F_in,
-                       const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
-                       float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                       kgx_stream_t stream);
+/* kgx_fused_args, read by kgx_spmm_gemm_run ("gemm") and kgx_spmm_gemm_f256_run
+ * ("f256"); both read every field but `slice` (zero-fill the struct first):
+ *   struct_size   sizeof(kgx_fused_args), else KGX_ERR_ARG.
+ *   reduce, flags KGX_SUM, MEAN, MAX or MIN; KGX_FUSED_* (unknown bits: KGX_ERR_ARG).
+ *   work          the work list (kgx_work), short rows and tiny records included: the
+ *       positional call's boundary (gcn_conv.py:233-272, aggregators.py:56-167).
+ *   x, ld_x       the feature table, 16-byte aligned, ld_x % 4 == 0, ld_x in
+ *       [F_in, 2^31).  KGX_FUSED_PRE_GIN's root rows are rows of x.
+ *   x2, n_x1      gather from TWO feature tables: source columns c < n_x1 are
+ *       rows of x, columns c >= n_x1 rows c - n_x1 of x2 (same ld_x, 16-byte
+ *       aligned; 0 <= n_x1 < 2^31).  The sharded layers' halo pass reads a
+ *       row's own-source edges from the layer input and its halo edges from
+ *       the exchange's receive buffer in ONE pass, so the row is written once
+ *       instead of written and read-modify-written (distributed.py;
+ *       gcn_conv.py:233-272, gin_conv.py:216-225 per shard).  With x2: sums
+ *       only (weighted or not, GIN's pre-scale allowed); gemm also needs F_in
+ *       128 and F_out % 16 == 0 (else KGX_ERR_UNSUPPORTED).  x2 NULL: one table.
+ *   F_in, W, F_out   W [F_in, F_out] row-major.  gemm: F_in and F_out multiples
+ *       of 4 <= 128.  f256: F_in == 256, F_out a multiple of 16 <= 256.
+ *   bias, gin_scale   [F_out], optional; KGX_FUSED_PRE_GIN's factor.  pad_ is not read.
+ *   out, ld_out   [n_rows, ld_out >= F_out], 16-byte aligned, ld_out % 4 == 0 (dwordx4 stores).
+ *   partials      one slot per hub chunk of n_slots, gemm 128 floats per slot,
+ *       f256 256; needed when the schedule has split rows or is sliced.
+ *   agg_out, ld_agg  (optional, [n, ld_agg >= F_in], 16-byte aligned, ld_agg % 4
+ *       == 0) also store PRE(REDUCE(...)), the rows before the transform --
+ *       what the backward's dW = agg^T dOut needs.
+ *   slice         [gemm] the sliced schedule (kgx_slice); [f256] n_classes must be 0.
+ * Both fail with KGX_ERR_ARG / KGX_ERR_UNSUPPORTED before any device work. */
+typedef struct kgx_fused_args {
+  uint64_t struct_size;
+  int32_t reduce, flags;
+  kgx_work work;
+  const float* x; int64_t ld_x; const float* x2; int64_t n_x1; int64_t F_in;
+  const float* W; int64_t F_out; const float* bias; float gin_scale; float pad_;
+  float* out; int64_t ld_out; float* partials; float* agg_out; int64_t ld_agg;
+  kgx_slice slice;
+} kgx_fused_args;
+int kgx_spmm_gemm_run(const kgx_fused_args* a, kgx_stream_t stream);
+int kgx_spmm_gemm_f256_run(const kgx_fused_args* a, kgx_stream_t stream);
 
-/* kgx_spmm_gemm_f256_ex: kgx_spmm_gemm_f256 gathering from TWO feature tables,
- * as kgx_spmm_gemm_ex3: source columns c < n_x1 are rows of x, c >= n_x1 rows
- * c - n_x1 of x2 (same ld_x, 16-byte aligned); pre_gin's root rows are rows of
- * x.  The sharded GINConv's merged halo pass at C4: a row's own-source and
- * halo edges in one launch, (1+eps) x_i + aggr -> Dense, the row written once
- * (distributed.py; gin_conv.py:216-225 per shard).  Sum only with x2; x2 NULL:
- * kgx_spmm_gemm_f256. */
-int kgx_spmm_gemm_f256_ex(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                          const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                          const int32_t* tiny_pack, const float* tiny_w, const int32_t* split, int64_t n_split,
-                          const int32_t* idx, const float* w, const float* x, int64_t ld_x, const float* x2,
-                          int64_t n_x1, int64_t F_in, const float* W, int64_t F_out, const float* bias, int flags,
-                          float gin_scale, float* out, int64_t ld_out, float* partials, float* agg_out,
-                          int64_t ld_agg, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Weight and bias gradients of a layer out = P W + b (the fused layers'

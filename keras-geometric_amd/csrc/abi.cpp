@@ -16,5 +16,5 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace kgx
 
-extern "C" int kgx_version(void) { return 1; }
+extern "C" int kgx_version(void) { return 2; }
 extern "C" const char* kgx_last_error(void) { return kgx::g_err; }

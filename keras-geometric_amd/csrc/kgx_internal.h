@@ -101,7 +101,7 @@ inline int64_t shared_cap(int64_t full) {
   return c > 0 ? c : 1;
 }
 
-// Grid of a sliced fused launch (kgx_spmm_gemm_ex4): n_classes item lists, block b
+// Grid of a sliced fused launch (kgx_fused_args.slice): n_classes item lists, block b
 // on list b % n_classes, so the grid is a multiple of n_classes -- the largest
 // one within `resident` blocks, no more than list_tiles blocks per list.  0: no
 // such grid (fewer resident blocks than lists); the launch then runs unsliced.

@@ -64,11 +64,11 @@ struct SpmmArgs {
   // EXACT mode (no items): rows[n_rows_long, n_rows) of the degree-ordered list have degree <=
   // KGX_SHORT_ROW_MAX and go to spmm_short_kernel (each row still one chain in CSR order)
   int64_t n_rows_long;
-  // two-table gathers (kgx_spmm_ex2): sources c >= n_t1 are rows c - n_t1 of a second
+  // two-table gathers (kgx_spmm_args.table2): sources c >= n_t1 are rows c - n_t1 of a second
   // table (same ld_t); t2b = table2 - n_t1 * ld_t as an address.  n_t1 = INT32_MAX: one table.
   const float* t2b;
   int32_t n_t1;
-  // EXACT mode, dynamic pickup (kgx_spmm_ex2 counters): dyn[0] hands out the hub
+  // EXACT mode, dynamic pickup (kgx_spmm_args.counters): dyn[0] hands out the hub
   // kernel's (row, column group) items; with dyn_rows = 1, dyn[1] hands out
   // spmm_kernel's interleaved row batches.  NULL: the static grid-stride schedule.
   int32_t* dyn;
@@ -939,136 +939,135 @@ bool aligned(const void* p, int bytes) { return p == nullptr || reinterpret_cast
 
 using namespace kgx;
 
-extern "C" int kgx_spmm(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                        const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
-                        const int32_t* idx, const float* w, const float* table, int64_t ld_table, int64_t F,
-                        float* out, int64_t ld_out, const float* bias, const float* xroot, int64_t ld_x,
-                        float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed,
-                        float* partials, kgx_stream_t stream_) {
-  return kgx_spmm_ex(reduce, epilogue, rowptr, rows, n_rows, items, n_items, n_items, split, n_split, idx, w, table,
-                     ld_table, F, out, ld_out, bias, xroot, ld_x, gin_scale, drop_key, drop_p, drop_seed, partials,
-                     stream_);
-}
-
-extern "C" int kgx_spmm_ex(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                           const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split,
-                           int64_t n_split, const int32_t* idx, const float* w, const float* table, int64_t ld_table,
-                           int64_t F, float* out, int64_t ld_out, const float* bias, const float* xroot,
-                           int64_t ld_x, float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed,
-                           float* partials, kgx_stream_t stream_) {
-  return kgx_spmm_ex2(reduce, epilogue, rowptr, rows, n_rows, items, n_items, n_long_items, split, n_split, idx, w,
-                      table, ld_table, nullptr, 0, F, out, ld_out, bias, xroot, ld_x, gin_scale, drop_key, drop_p,
-                      drop_seed, partials, nullptr, stream_);
-}
-
-extern "C" int kgx_spmm_ex2(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                            const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split,
-                            int64_t n_split, const int32_t* idx, const float* w, const float* table, int64_t ld_table,
-                            const float* table2, int64_t n_table1, int64_t F, float* out, int64_t ld_out,
-                            const float* bias, const float* xroot, int64_t ld_x, float gin_scale,
-                            const int32_t* drop_key, float drop_p, uint64_t drop_seed, float* partials,
-                            int32_t* counters, kgx_stream_t stream_) {
+extern "C" int kgx_spmm_run(const kgx_spmm_args* p, kgx_stream_t stream_) {
+  KGX_REQUIRE(p, KGX_ERR_ARG, "kgx_spmm: the kgx_spmm_args pointer is NULL");
+  KGX_REQUIRE(p->struct_size == sizeof(*p), KGX_ERR_ARG,
+              "kgx_spmm: struct_size %llu is not sizeof(kgx_spmm_args) = %zu (a binding of another kgx.h?)",
+              (unsigned long long)p->struct_size, sizeof(*p));
+  const kgx_work& g = p->work;
+  KGX_REQUIRE(!g.tiny_pack && (!g.items || g.n_short_end == g.n_items), KGX_ERR_ARG,
+              "kgx_spmm: work.tiny_pack must be NULL and work.n_short_end equal n_items (no tiny-record path)");
   hipStream_t stream = as_stream(stream_);
-  KGX_REQUIRE(!table2 || (n_table1 >= 0 && n_table1 < (int64_t(1) << 31) && items), KGX_ERR_ARG,
+  KGX_REQUIRE(!p->table2 || (p->n_table1 >= 0 && p->n_table1 < (int64_t(1) << 31) && g.items), KGX_ERR_ARG,
               "kgx_spmm: a second table needs 0 <= n_table1 < 2^31 and the schedule (not EXACT mode)");
-  KGX_REQUIRE(!table2 || (reduce == KGX_SUM && !drop_key), KGX_ERR_UNSUPPORTED,
+  KGX_REQUIRE(!p->table2 || (p->reduce == KGX_SUM && !p->drop_key), KGX_ERR_UNSUPPORTED,
               "kgx_spmm: two-table gathers are implemented for plain / weighted sums");
-  KGX_REQUIRE(!items || (n_long_items >= 0 && n_long_items <= n_items), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.items || (g.n_long_items >= 0 && g.n_long_items <= g.n_items), KGX_ERR_ARG,
               "kgx_spmm: n_long_items must lie in [0, n_items]");
-  KGX_REQUIRE(reduce >= KGX_SUM && reduce <= KGX_STD, KGX_ERR_ARG, "kgx_spmm: unknown reduce %d", reduce);
-  KGX_REQUIRE(epilogue >= KGX_EPI_NONE && epilogue <= KGX_EPI_ACCUM, KGX_ERR_ARG, "kgx_spmm: unknown epilogue %d",
-              epilogue);
-  KGX_REQUIRE(epilogue != KGX_EPI_ACCUM || reduce == KGX_SUM, KGX_ERR_ARG,
-              "kgx_spmm: KGX_EPI_ACCUM accumulates plain sums only (got reduce %d)", reduce);
-  KGX_REQUIRE(F >= 0 && n_rows >= 0 && n_items >= 0 && n_split >= 0, KGX_ERR_ARG, "kgx_spmm: negative size");
-  if (F == 0 || n_rows == 0) return KGX_OK;
-  KGX_REQUIRE(out && ld_out >= F && ld_table >= F, KGX_ERR_ARG, "kgx_spmm: bad output / leading dimensions");
-  KGX_REQUIRE(ld_table < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_spmm: table leading dimension >= 2^31");
-  KGX_REQUIRE(rowptr && rows && idx && table, KGX_ERR_ARG, "kgx_spmm: null CSR / table pointer");
-  KGX_REQUIRE(epilogue != KGX_EPI_BIAS || bias, KGX_ERR_ARG, "kgx_spmm: EPI_BIAS needs bias");
-  KGX_REQUIRE(epilogue != KGX_EPI_GIN || (xroot && ld_x >= F), KGX_ERR_ARG, "kgx_spmm: EPI_GIN needs xroot");
-  KGX_REQUIRE(!drop_key || (reduce == KGX_SUM && drop_p >= 0.0f && drop_p < 1.0f), KGX_ERR_ARG,
-              "kgx_spmm: message dropout needs reduce SUM and 0 <= p < 1 (got reduce %d, p %g)", reduce,
-              double(drop_p));
-  const bool use_items = items != nullptr && reduce != KGX_STD;
-  KGX_REQUIRE(!use_items || n_split == 0 || (split && partials), KGX_ERR_ARG,
+  KGX_REQUIRE(p->reduce >= KGX_SUM && p->reduce <= KGX_STD, KGX_ERR_ARG, "kgx_spmm: unknown reduce %d", p->reduce);
+  KGX_REQUIRE(p->epilogue >= KGX_EPI_NONE && p->epilogue <= KGX_EPI_ACCUM, KGX_ERR_ARG, "kgx_spmm: unknown epilogue %d",
+              p->epilogue);
+  KGX_REQUIRE(p->epilogue != KGX_EPI_ACCUM || p->reduce == KGX_SUM, KGX_ERR_ARG,
+              "kgx_spmm: KGX_EPI_ACCUM accumulates plain sums only (got reduce %d)", p->reduce);
+  KGX_REQUIRE(p->F >= 0 && g.n_rows >= 0 && g.n_items >= 0 && g.n_split >= 0, KGX_ERR_ARG, "kgx_spmm: negative size");
+  if (p->F == 0 || g.n_rows == 0) return KGX_OK;
+  KGX_REQUIRE(p->out && p->ld_out >= p->F && p->ld_table >= p->F, KGX_ERR_ARG,
+              "kgx_spmm: bad output / leading dimensions");
+  KGX_REQUIRE(p->ld_table < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_spmm: table leading dimension >= 2^31");
+  KGX_REQUIRE(g.rowptr && g.rows && g.idx && p->table, KGX_ERR_ARG, "kgx_spmm: null CSR / table pointer");
+  KGX_REQUIRE(p->epilogue != KGX_EPI_BIAS || p->bias, KGX_ERR_ARG, "kgx_spmm: EPI_BIAS needs bias");
+  KGX_REQUIRE(p->epilogue != KGX_EPI_GIN || (p->xroot && p->ld_x >= p->F), KGX_ERR_ARG,
+              "kgx_spmm: EPI_GIN needs xroot");
+  KGX_REQUIRE(!p->drop_key || (p->reduce == KGX_SUM && p->drop_p >= 0.0f && p->drop_p < 1.0f), KGX_ERR_ARG,
+              "kgx_spmm: message dropout needs reduce SUM and 0 <= p < 1 (got reduce %d, p %g)", p->reduce,
+              double(p->drop_p));
+  const bool use_items = g.items != nullptr && p->reduce != KGX_STD;
+  KGX_REQUIRE(!use_items || g.n_split == 0 || (g.split && p->partials), KGX_ERR_ARG,
               "kgx_spmm: split rows need split list and partials");
 
   SpmmArgs a{};
-  a.rowptr = rowptr;
-  a.rows = rows;
-  a.n_rows = n_rows;
-  a.items = use_items ? reinterpret_cast<const int4*>(items) : nullptr;
-  a.n_items = use_items ? n_items : 0;
-  a.split = reinterpret_cast<const int4*>(split);
-  a.n_split = use_items ? n_split : 0;
-  a.n_long = use_items ? n_long_items : 0;
+  a.rowptr = g.rowptr;
+  a.rows = g.rows;
+  a.n_rows = g.n_rows;
+  a.items = use_items ? reinterpret_cast<const int4*>(g.items) : nullptr;
+  a.n_items = use_items ? g.n_items : 0;
+  a.split = reinterpret_cast<const int4*>(g.split);
+  a.n_split = use_items ? g.n_split : 0;
+  a.n_long = use_items ? g.n_long_items : 0;
   // EXACT mode: 0 < n_long_items < n_rows names the short-row suffix of the degree-ordered rows
-  a.n_rows_long = (!use_items && reduce != KGX_STD && n_long_items > 0 && n_long_items < n_rows) ? n_long_items : n_rows;
-  a.idx = idx;
-  a.w = w;
-  a.epi = epilogue;
-  a.gin_scale = gin_scale;
-  a.ld_t = ld_table;
-  a.ld_o = ld_out;
-  a.ld_x = ld_x;
-  a.ld_p = F;
+  const bool suffix = !use_items && p->reduce != KGX_STD && g.n_long_items > 0 && g.n_long_items < g.n_rows;
+  a.n_rows_long = suffix ? g.n_long_items : g.n_rows;
+  a.idx = g.idx;
+  a.w = g.w;
+  a.epi = p->epilogue;
+  a.gin_scale = p->gin_scale;
+  a.ld_t = p->ld_table;
+  a.ld_o = p->ld_out;
+  a.ld_x = p->ld_x;
+  a.ld_p = p->F;
   static const int hints = [] {
     const char* h = getenv("KGX_SPMM_HINTS");
     return h ? atoi(h) : 0;
   }();
   a.hints = hints;
-  if (drop_key && drop_p > 0.0f) {
-    a.drop_key = drop_key;
-    a.drop_seed = drop_seed;
-    a.drop_thresh = uint32_t(double(drop_p) * 4294967296.0);
-    a.drop_scale = 1.0f / (1.0f - drop_p);
+  if (p->drop_key && p->drop_p > 0.0f) {
+    a.drop_key = p->drop_key;
+    a.drop_seed = p->drop_seed;
+    a.drop_thresh = uint32_t(double(p->drop_p) * 4294967296.0);
+    a.drop_scale = 1.0f / (1.0f - p->drop_p);
   }
 
   // widest vector the shapes and pointers allow
-  a.n_t1 = table2 ? int32_t(n_table1) : INT32_MAX;
-  a.dyn = (!use_items && reduce != KGX_STD) ? counters : nullptr;
+  a.n_t1 = p->table2 ? int32_t(p->n_table1) : INT32_MAX;
+  a.dyn = (!use_items && p->reduce != KGX_STD) ? p->counters : nullptr;
   auto ok = [&](int v) {
     const int b = 4 * v;
-    return F % v == 0 && ld_table % v == 0 && ld_out % v == 0 && aligned(table, b) && aligned(out, b) &&
-           (!table2 || aligned(table2, b)) &&
-           (epilogue != KGX_EPI_BIAS || aligned(bias, b)) &&
-           (epilogue != KGX_EPI_GIN || (ld_x % v == 0 && aligned(xroot, b))) && aligned(partials, b);
+    return p->F % v == 0 && p->ld_table % v == 0 && p->ld_out % v == 0 && aligned(p->table, b) && aligned(p->out, b) &&
+           (!p->table2 || aligned(p->table2, b)) &&
+           (p->epilogue != KGX_EPI_BIAS || aligned(p->bias, b)) &&
+           (p->epilogue != KGX_EPI_GIN || (p->ld_x % v == 0 && aligned(p->xroot, b))) && aligned(p->partials, b);
   };
   const int VEC = ok(4) ? 4 : (ok(2) ? 2 : 1);
-  const int64_t fvec = F / VEC;
+  const int64_t fvec = p->F / VEC;
   const int G = int(fvec >= 64 ? 64 : next_pow2(int(fvec)));
   int lg = 0;
   while ((1 << lg) < G) ++lg;
   // column slices of at most 4*64*VEC features per launch
   const int64_t slice = int64_t(4) * 64 * VEC;
-  for (int64_t c0 = 0; c0 < F; c0 += slice) {
-    const int64_t cw = (F - c0) < slice ? (F - c0) : slice;
+  for (int64_t c0 = 0; c0 < p->F; c0 += slice) {
+    const int64_t cw = (p->F - c0) < slice ? (p->F - c0) : slice;
     const int64_t cv = cw / VEC;
     const int nt = cv <= 64 ? 1 : (cv <= 128 ? 2 : 4);
     SpmmArgs s = a;
     s.F = int(cw);
     s.G = G;
     s.lgG = lg;
-    s.table = table + c0;
+    s.table = p->table + c0;
     // table2 - n_t1 * ld_t (+ the slice's first column), as an address; tsrc adds row_off(c)
-    s.t2b = table2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(table2 + c0) -
-                                                    uintptr_t(n_table1) * uintptr_t(ld_table) * sizeof(float))
+    s.t2b = p->table2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(p->table2 + c0) -
+                                                    uintptr_t(p->n_table1) * uintptr_t(p->ld_table) * sizeof(float))
                    : s.table;
-    s.out = out + c0;
-    s.bias = bias ? bias + c0 : nullptr;
-    s.xroot = xroot ? xroot + c0 : nullptr;
-    s.partials = partials ? partials + c0 : nullptr;
+    s.out = p->out + c0;
+    s.bias = p->bias ? p->bias + c0 : nullptr;
+    s.xroot = p->xroot ? p->xroot + c0 : nullptr;
+    s.partials = p->partials ? p->partials + c0 : nullptr;
     s.f_base = int(c0);
     if (s.dyn && c0 > 0 && hipMemsetAsync(s.dyn, 0, 2 * sizeof(int32_t), stream) != hipSuccess) {
       set_error("kgx_spmm: counter reset failed");  // each column slice hands its rows out again
       return KGX_ERR_HIP;
     }
     int rc;
-    if (VEC == 4) rc = dispatch_nt<4>(nt, reduce, s, stream);
-    else if (VEC == 2) rc = dispatch_nt<2>(nt, reduce, s, stream);
-    else rc = dispatch_nt<1>(nt, reduce, s, stream);
+    if (VEC == 4) rc = dispatch_nt<4>(nt, p->reduce, s, stream);
+    else if (VEC == 2) rc = dispatch_nt<2>(nt, p->reduce, s, stream);
+    else rc = dispatch_nt<1>(nt, p->reduce, s, stream);
     if (rc != KGX_OK) return rc;
   }
   return KGX_OK;
+}
+
+extern "C" int kgx_spmm(int reduce, int epilogue, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                        const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                        const int32_t* idx, const float* w, const float* table, int64_t ld_table, int64_t F,
+                        float* out, int64_t ld_out, const float* bias, const float* xroot, int64_t ld_x,
+                        float gin_scale, const int32_t* drop_key, float drop_p, uint64_t drop_seed,
+                        float* partials, kgx_stream_t stream_) {
+  kgx_spmm_args a{};  // (zeroed: one table, no counters)
+  a.struct_size = sizeof(a);
+  a.reduce = reduce; a.epilogue = epilogue;
+  a.work = kgx_work{rowptr, rows, n_rows, items, n_items, n_items, n_items, nullptr, nullptr, 0, split, n_split, idx, w};
+  a.table = table; a.ld_table = ld_table; a.F = F;
+  a.out = out; a.ld_out = ld_out; a.partials = partials;
+  a.bias = bias; a.xroot = xroot; a.ld_x = ld_x; a.gin_scale = gin_scale;
+  a.drop_key = drop_key; a.drop_p = drop_p; a.drop_seed = drop_seed;
+  return kgx_spmm_run(&a, stream_);
 }

@@ -25,7 +25,7 @@
 // phase; barriers are LDS-only so those gathers stay in flight.  Hub-row
 // chunks write raw partials; the fix-up kernel combines them in slot order and
 // applies W with the same split product.  With a sliced schedule
-// (kgx_spmm_gemm_ex4) the rows above a degree threshold are cut by SOURCE CLASS
+// (kgx_fused_args.slice) the rows above a degree threshold are cut by SOURCE CLASS
 // instead and block b walks list b % C, so each XCD's L2 keeps one class of the
 // hot source rows (an affinity: results never depend on where a block runs).
 #include <cstdlib>
@@ -85,13 +85,13 @@ struct FusedArgs {
   const float2* tw;     // their weights {w0, w1} (weighted reductions)
   int64_t n_tiny;       // rows in tpack
   int64_t n_tiny2;      // the first n_tiny2 of them have degree 2 (the rest <= 1)
-  // two-table gathers (kgx_spmm_gemm_ex3): sources col >= n_x1 are rows of a
+  // two-table gathers (kgx_fused_args.x2): sources col >= n_x1 are rows of a
   // second table x2 (same ld_x); x2b = x2 - n_x1 * ld_x (host address math), so
   // the gather address is one select of the base.  n_x1 = INT32_MAX: one table.
   const float* x2b;
   int32_t n_x1;
   bool cu_split;  // KGX_FUSED_CU_SPLIT (host side only)
-  // sliced schedule (kgx_spmm_gemm_ex4, kgx_slice_build): C complete item lists for the
+  // sliced schedule (kgx_fused_args.slice, kgx_slice_build): C complete item lists for the
   // main kernel, list c = the class-c chunks of the sliced rows (offsets into sl_idx /
   // sl_w, slot >= 0), then its share of the other long items (offsets into idx / w).
   // split / n_split are then the sliced rows' fix-up records.  sl_classes = 0: unsliced.
@@ -996,173 +996,145 @@ int launch(const FusedArgs& a_in, hipStream_t s) {
 
 using namespace kgx;
 
-extern "C" int kgx_spmm_gemm(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                             const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
-                             const int32_t* idx, const float* w, const float* x, int64_t ld_x, int64_t F_in,
-                             const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
-                             float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                             kgx_stream_t stream_) {
-  return kgx_spmm_gemm_ex(reduce, rowptr, rows, n_rows, items, n_items, n_items, split, n_split, idx, w, x, ld_x,
-                          F_in, W, F_out, bias, flags, gin_scale, out, ld_out, partials, agg_out, ld_agg, stream_);
-}
-
-extern "C" int kgx_spmm_gemm_ex(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                const int32_t* items, int64_t n_items, int64_t n_long_items, const int32_t* split,
-                                int64_t n_split, const int32_t* idx, const float* w, const float* x, int64_t ld_x,
-                                int64_t F_in, const float* W, int64_t F_out, const float* bias, int flags,
-                                float gin_scale, float* out, int64_t ld_out, float* partials, float* agg_out,
-                                int64_t ld_agg, kgx_stream_t stream_) {
-  return kgx_spmm_gemm_ex2(reduce, rowptr, rows, n_rows, items, n_items, n_long_items, n_items, nullptr, nullptr, 0,
-                           split, n_split, idx, w, x, ld_x, F_in, W, F_out, bias, flags, gin_scale, out, ld_out,
-                           partials, agg_out, ld_agg, stream_);
-}
-
-extern "C" int kgx_spmm_gemm_ex2(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                 const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                                 const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                                 const int32_t* split,
-                                 int64_t n_split, const int32_t* idx, const float* w, const float* x, int64_t ld_x,
-                                 int64_t F_in, const float* W, int64_t F_out, const float* bias, int flags,
-                                 float gin_scale, float* out, int64_t ld_out, float* partials, float* agg_out,
-                                 int64_t ld_agg, kgx_stream_t stream_) {
-  return kgx_spmm_gemm_ex3(reduce, rowptr, rows, n_rows, items, n_items, n_long_items, n_short_end, tiny_pack, tiny_w,
-                           n_tiny_deg2, split, n_split, idx, w, x, ld_x, nullptr, 0, F_in, W, F_out, bias, flags,
-                           gin_scale, out, ld_out, partials, agg_out, ld_agg, stream_);
-}
-
-extern "C" int kgx_spmm_gemm_ex3(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                 const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                                 const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                                 const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
-                                 const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
-                                 const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
-                                 float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                                 kgx_stream_t stream_) {
-  return kgx_spmm_gemm_ex4(reduce, rowptr, rows, n_rows, items, n_items, n_long_items, n_short_end, tiny_pack, tiny_w,
-                           n_tiny_deg2, split, n_split, idx, w, x, ld_x, x2, n_x1, F_in, W, F_out, bias, flags,
-                           gin_scale, out, ld_out, partials, agg_out, ld_agg, nullptr, nullptr, 0, 0, nullptr, nullptr,
-                           nullptr, 0, -1, stream_);
-}
 
 extern "C" int kgx_slice_grid(int64_t resident_blocks, int64_t list_tiles, int n_classes) {
   return int(slice_grid(resident_blocks, list_tiles, n_classes));
 }
 
-extern "C" int kgx_spmm_gemm_ex4(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                 const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                                 const int32_t* tiny_pack, const float* tiny_w, int64_t n_tiny_deg2,
-                                 const int32_t* split, int64_t n_split, const int32_t* idx, const float* w,
-                                 const float* x, int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in,
-                                 const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
-                                 float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                                 const int32_t* sl_items, const int32_t* sl_lists, int n_classes, int64_t sl_tiles,
-                                 const int32_t* sl_idx, const float* sl_w, const int32_t* sl_split,
-                                 int64_t sl_n_split, int64_t head_short_end, kgx_stream_t stream_) {
+extern "C" int kgx_spmm_gemm_run(const kgx_fused_args* p, kgx_stream_t stream_) {
+  KGX_REQUIRE(p, KGX_ERR_ARG, "kgx_spmm_gemm: the kgx_fused_args pointer is NULL");
+  KGX_REQUIRE(p->struct_size == sizeof(*p), KGX_ERR_ARG,
+              "kgx_spmm_gemm: struct_size %llu is not sizeof(kgx_fused_args) = %zu (a binding of another kgx.h?)",
+              (unsigned long long)p->struct_size, sizeof(*p));
+  const kgx_work& g = p->work;
+  const kgx_slice& sl = p->slice;
   hipStream_t stream = as_stream(stream_);
-  KGX_REQUIRE(n_classes == 0 || ((n_classes == 4 || n_classes == 8) && items && sl_items && sl_lists && sl_idx &&
-                                 sl_split && sl_n_split > 0 && sl_tiles > 0 && partials && (!w || sl_w)),
-              KGX_ERR_ARG, "kgx_spmm_gemm_ex4: a sliced launch needs 4 or 8 lists, their items, the sliced arrays, "
+  KGX_REQUIRE(sl.n_classes == 0 || ((sl.n_classes == 4 || sl.n_classes == 8) && g.items && sl.items && sl.lists &&
+                                    sl.idx && sl.split && sl.n_split > 0 && sl.tiles > 0 && p->partials &&
+                                    (!g.w || sl.w)),
+              KGX_ERR_ARG, "kgx_spmm_gemm: a sliced launch needs 4 or 8 lists, their items, the sliced arrays, "
                            "fix-up records and partials");
-  KGX_REQUIRE(n_classes == 0 || (!x2 && reduce == KGX_SUM && F_in == kFin && F_out % 16 == 0), KGX_ERR_UNSUPPORTED,
-              "kgx_spmm_gemm_ex4: the sliced schedule is implemented for one-table sums at F_in 128, F_out %% 16 == 0");
-  KGX_REQUIRE(n_classes == 0 || head_short_end <= n_short_end, KGX_ERR_ARG,
-              "kgx_spmm_gemm_ex4: head_short_end must not exceed n_short_end");
-  KGX_REQUIRE(!x2 || (n_x1 >= 0 && n_x1 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(x2) % 16 == 0),
+  KGX_REQUIRE(sl.n_classes == 0 || (!p->x2 && p->reduce == KGX_SUM && p->F_in == kFin && p->F_out % 16 == 0),
+              KGX_ERR_UNSUPPORTED,
+              "kgx_spmm_gemm: the sliced schedule is implemented for one-table sums at F_in 128, F_out %% 16 == 0");
+  KGX_REQUIRE(sl.n_classes == 0 || sl.head_short_end <= g.n_short_end, KGX_ERR_ARG,
+              "kgx_spmm_gemm: head_short_end must not exceed n_short_end");
+  KGX_REQUIRE(!p->x2 || (p->n_x1 >= 0 && p->n_x1 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(p->x2) % 16 == 0),
               KGX_ERR_ARG, "kgx_spmm_gemm: x2 must be 16-byte aligned and 0 <= n_x1 < 2^31");
   // (GIN's pre-scale reads the rows' own x: rows of the first table, local rows)
-  KGX_REQUIRE(!x2 || (reduce == KGX_SUM && F_in == kFin && F_out % 16 == 0), KGX_ERR_UNSUPPORTED,
+  KGX_REQUIRE(!p->x2 || (p->reduce == KGX_SUM && p->F_in == kFin && p->F_out % 16 == 0), KGX_ERR_UNSUPPORTED,
               "kgx_spmm_gemm: two-table gathers are implemented for sums at F_in 128, F_out %% 16 == 0 "
               "(the sharded GCN / GIN passes)");
-  KGX_REQUIRE(!items || tiny_pack || n_short_end == n_items, KGX_ERR_ARG,
+  KGX_REQUIRE(!g.items || g.tiny_pack || g.n_short_end == g.n_items, KGX_ERR_ARG,
               "kgx_spmm_gemm: without tiny_pack, n_short_end must equal n_items");
-  KGX_REQUIRE(!items || (n_long_items >= 0 && n_long_items <= n_short_end && n_short_end <= n_items), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.items || (g.n_long_items >= 0 && g.n_long_items <= g.n_short_end && g.n_short_end <= g.n_items),
+              KGX_ERR_ARG,
               "kgx_spmm_gemm: need 0 <= n_long_items <= n_short_end <= n_items");
-  KGX_REQUIRE(!tiny_pack || (items && (w == nullptr || tiny_w)), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.tiny_pack || (g.items && (g.w == nullptr || g.tiny_w)), KGX_ERR_ARG,
               "kgx_spmm_gemm: the tiny-row records need the schedule (and weights when weighted)");
-  KGX_REQUIRE(!tiny_pack || (n_tiny_deg2 >= 0 && n_tiny_deg2 <= n_items - n_short_end), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.tiny_pack || (g.n_tiny_deg2 >= 0 && g.n_tiny_deg2 <= g.n_items - g.n_short_end), KGX_ERR_ARG,
               "kgx_spmm_gemm: n_tiny_deg2 must lie in [0, n_items - n_short_end]");
-  KGX_REQUIRE(reduce >= KGX_SUM && reduce <= KGX_MIN, KGX_ERR_ARG, "kgx_spmm_gemm: reduce %d unsupported", reduce);
-  KGX_REQUIRE(F_in > 0 && F_in <= kFin && F_in % 4 == 0, KGX_ERR_UNSUPPORTED,
-              "kgx_spmm_gemm: F_in must be a multiple of 4 <= %d (got %lld)", kFin, (long long)F_in);
-  KGX_REQUIRE(F_out > 0 && F_out <= 128 && F_out % 4 == 0, KGX_ERR_UNSUPPORTED,
-              "kgx_spmm_gemm: F_out must be a multiple of 4 <= 128 (got %lld)", (long long)F_out);
-  KGX_REQUIRE(n_rows >= 0 && n_items >= 0 && n_split >= 0, KGX_ERR_ARG, "kgx_spmm_gemm: negative size");
-  KGX_REQUIRE((flags & ~(KGX_FUSED_PRE_GIN | KGX_FUSED_ACCUMULATE | KGX_FUSED_SHARE_GPU | KGX_FUSED_RELU |
+  KGX_REQUIRE(p->reduce >= KGX_SUM && p->reduce <= KGX_MIN, KGX_ERR_ARG, "kgx_spmm_gemm: reduce %d unsupported",
+              p->reduce);
+  KGX_REQUIRE(p->F_in > 0 && p->F_in <= kFin && p->F_in % 4 == 0, KGX_ERR_UNSUPPORTED,
+              "kgx_spmm_gemm: F_in must be a multiple of 4 <= %d (got %lld)", kFin, (long long)p->F_in);
+  KGX_REQUIRE(p->F_out > 0 && p->F_out <= 128 && p->F_out % 4 == 0, KGX_ERR_UNSUPPORTED,
+              "kgx_spmm_gemm: F_out must be a multiple of 4 <= 128 (got %lld)", (long long)p->F_out);
+  KGX_REQUIRE(g.n_rows >= 0 && g.n_items >= 0 && g.n_split >= 0, KGX_ERR_ARG, "kgx_spmm_gemm: negative size");
+  KGX_REQUIRE((p->flags & ~(KGX_FUSED_PRE_GIN | KGX_FUSED_ACCUMULATE | KGX_FUSED_SHARE_GPU | KGX_FUSED_RELU |
                          KGX_FUSED_CU_SPLIT)) == 0,
-              KGX_ERR_ARG, "kgx_spmm_gemm: unknown flags 0x%x", flags);
-  KGX_REQUIRE(!agg_out || (ld_agg >= F_in && reinterpret_cast<uintptr_t>(agg_out) % 16 == 0 && ld_agg % 4 == 0),
+              KGX_ERR_ARG, "kgx_spmm_gemm: unknown flags 0x%x", p->flags);
+  KGX_REQUIRE(!p->agg_out || (p->ld_agg >= p->F_in && reinterpret_cast<uintptr_t>(p->agg_out) % 16 == 0 &&
+                              p->ld_agg % 4 == 0),
               KGX_ERR_ARG, "kgx_spmm_gemm: agg_out must be 16-byte aligned with ld >= F_in, ld %% 4 == 0");
-  if (n_rows == 0) return KGX_OK;
-  KGX_REQUIRE(rowptr && rows && idx && x && W && out, KGX_ERR_ARG, "kgx_spmm_gemm: null pointer");
-  KGX_REQUIRE(ld_x >= F_in && ld_x < (int64_t(1) << 31), KGX_ERR_ARG,
+  if (g.n_rows == 0) return KGX_OK;
+  KGX_REQUIRE(g.rowptr && g.rows && g.idx && p->x && p->W && p->out, KGX_ERR_ARG, "kgx_spmm_gemm: null pointer");
+  KGX_REQUIRE(p->ld_x >= p->F_in && p->ld_x < (int64_t(1) << 31), KGX_ERR_ARG,
               "kgx_spmm_gemm: x leading dimension must lie in [F_in, 2^31)");
-  KGX_REQUIRE(ld_x % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && ld_out >= F_out, KGX_ERR_ARG,
+  KGX_REQUIRE(p->ld_x % 4 == 0 && reinterpret_cast<uintptr_t>(p->x) % 16 == 0 && p->ld_out >= p->F_out, KGX_ERR_ARG,
               "kgx_spmm_gemm: x must be 16-byte aligned with ld %% 4 == 0");
-  KGX_REQUIRE(ld_out % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0, KGX_ERR_ARG,
+  KGX_REQUIRE(p->ld_out % 4 == 0 && reinterpret_cast<uintptr_t>(p->out) % 16 == 0, KGX_ERR_ARG,
               "kgx_spmm_gemm: out must be 16-byte aligned with ld %% 4 == 0 (row stores are dwordx4)");
-  KGX_REQUIRE(!items || n_split == 0 || (split && partials), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.items || g.n_split == 0 || (g.split && p->partials), KGX_ERR_ARG,
               "kgx_spmm_gemm: split rows need split list and partials");
   FusedArgs a{};
-  a.rowptr = rowptr;
-  a.rows = rows;
-  a.n_rows = n_rows;
-  a.items = reinterpret_cast<const int4*>(items);
-  a.n_items = items ? n_items : 0;
-  a.n_long = items ? n_long_items : 0;
-  a.n_short_end = items ? n_short_end : 0;
-  a.tpack = items ? reinterpret_cast<const int4*>(tiny_pack) : nullptr;
-  a.tw = reinterpret_cast<const float2*>(tiny_w);
-  a.n_tiny = (items && tiny_pack) ? n_items - n_short_end : 0;
-  a.n_tiny2 = a.n_tiny ? n_tiny_deg2 : 0;
-  a.split = reinterpret_cast<const int4*>(split);
-  a.n_split = items ? n_split : 0;
-  a.idx = idx;
-  a.w = w;
-  a.x = x;
-  a.ld_x = ld_x;
-  a.n_x1 = x2 ? int32_t(n_x1) : INT32_MAX;
+  a.rowptr = g.rowptr;
+  a.rows = g.rows;
+  a.n_rows = g.n_rows;
+  a.items = reinterpret_cast<const int4*>(g.items);
+  a.n_items = g.items ? g.n_items : 0;
+  a.n_long = g.items ? g.n_long_items : 0;
+  a.n_short_end = g.items ? g.n_short_end : 0;
+  a.tpack = g.items ? reinterpret_cast<const int4*>(g.tiny_pack) : nullptr;
+  a.tw = reinterpret_cast<const float2*>(g.tiny_w);
+  a.n_tiny = (g.items && g.tiny_pack) ? g.n_items - g.n_short_end : 0;
+  a.n_tiny2 = a.n_tiny ? g.n_tiny_deg2 : 0;
+  a.split = reinterpret_cast<const int4*>(g.split);
+  a.n_split = g.items ? g.n_split : 0;
+  a.idx = g.idx;
+  a.w = g.w;
+  a.x = p->x;
+  a.ld_x = p->ld_x;
+  a.n_x1 = p->x2 ? int32_t(p->n_x1) : INT32_MAX;
   // x2 - n_x1 * ld_x as an address (modular): gather_src adds row_off(c) for c >= n_x1
-  a.x2b = x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(x2) -
-                                               uintptr_t(n_x1) * uintptr_t(ld_x) * sizeof(float))
-             : x;
-  a.W = W;
-  a.F_in = int(F_in);
-  a.F_out = int(F_out);
-  a.bias = bias;
-  a.out = out;
-  a.ld_o = ld_out;
-  a.partials = partials;
-  a.agg_out = agg_out;
-  a.ld_agg = ld_agg;
-  a.pre_gin = (flags & KGX_FUSED_PRE_GIN) != 0;
-  a.accumulate = (flags & KGX_FUSED_ACCUMULATE) != 0;
-  a.share_gpu = (flags & KGX_FUSED_SHARE_GPU) != 0;
-  a.relu = (flags & KGX_FUSED_RELU) != 0;
-  a.cu_split = (flags & KGX_FUSED_CU_SPLIT) != 0;
-  a.gin_scale = gin_scale;
-  a.sl_classes = items ? n_classes : 0;
-  a.sl_items = reinterpret_cast<const int4*>(sl_items);
-  a.sl_lists = reinterpret_cast<const int4*>(sl_lists);
-  a.sl_tiles = sl_tiles;
-  a.sl_idx = sl_idx;
-  a.sl_w = sl_w;
-  a.sl_split = reinterpret_cast<const int4*>(sl_split);
-  a.sl_n_split = sl_n_split;
-  a.sl_head_short_end = head_short_end;
-  const bool wt = w != nullptr;
-  if (x2) return wt ? launch<KGX_SUM, true, true>(a, stream) : launch<KGX_SUM, false, true>(a, stream);
-  if (F_in < kFin || F_out % 16 != 0) {  // the masked instantiations (SAGEConv at C5: 100 -> 100)
-    switch (reduce) {
+  a.x2b = p->x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(p->x2) -
+                                               uintptr_t(p->n_x1) * uintptr_t(p->ld_x) * sizeof(float))
+             : p->x;
+  a.W = p->W;
+  a.F_in = int(p->F_in);
+  a.F_out = int(p->F_out);
+  a.bias = p->bias;
+  a.out = p->out;
+  a.ld_o = p->ld_out;
+  a.partials = p->partials;
+  a.agg_out = p->agg_out;
+  a.ld_agg = p->ld_agg;
+  a.pre_gin = (p->flags & KGX_FUSED_PRE_GIN) != 0;
+  a.accumulate = (p->flags & KGX_FUSED_ACCUMULATE) != 0;
+  a.share_gpu = (p->flags & KGX_FUSED_SHARE_GPU) != 0;
+  a.relu = (p->flags & KGX_FUSED_RELU) != 0;
+  a.cu_split = (p->flags & KGX_FUSED_CU_SPLIT) != 0;
+  a.gin_scale = p->gin_scale;
+  a.sl_classes = g.items ? int(sl.n_classes) : 0;
+  a.sl_items = reinterpret_cast<const int4*>(sl.items);
+  a.sl_lists = reinterpret_cast<const int4*>(sl.lists);
+  a.sl_tiles = sl.tiles;
+  a.sl_idx = sl.idx;
+  a.sl_w = sl.w;
+  a.sl_split = reinterpret_cast<const int4*>(sl.split);
+  a.sl_n_split = sl.n_split;
+  a.sl_head_short_end = sl.head_short_end;
+  const bool wt = g.w != nullptr;
+  if (p->x2) return wt ? launch<KGX_SUM, true, true>(a, stream) : launch<KGX_SUM, false, true>(a, stream);
+  if (p->F_in < kFin || p->F_out % 16 != 0) {  // the masked instantiations (SAGEConv at C5: 100 -> 100)
+    switch (p->reduce) {
       case KGX_SUM: return wt ? launch<KGX_SUM, true, false, true>(a, stream) : launch<KGX_SUM, false, false, true>(a, stream);
       case KGX_MEAN: return wt ? launch<KGX_MEAN, true, false, true>(a, stream) : launch<KGX_MEAN, false, false, true>(a, stream);
       case KGX_MAX: return wt ? launch<KGX_MAX, true, false, true>(a, stream) : launch<KGX_MAX, false, false, true>(a, stream);
       default: return wt ? launch<KGX_MIN, true, false, true>(a, stream) : launch<KGX_MIN, false, false, true>(a, stream);
     }
   }
-  switch (reduce) {
+  switch (p->reduce) {
     case KGX_SUM: return wt ? launch<KGX_SUM, true>(a, stream) : launch<KGX_SUM, false>(a, stream);
     case KGX_MEAN: return wt ? launch<KGX_MEAN, true>(a, stream) : launch<KGX_MEAN, false>(a, stream);
     case KGX_MAX: return wt ? launch<KGX_MAX, true>(a, stream) : launch<KGX_MAX, false>(a, stream);
     default: return wt ? launch<KGX_MIN, true>(a, stream) : launch<KGX_MIN, false>(a, stream);
   }
+}
+
+extern "C" int kgx_spmm_gemm(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                             const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                             const int32_t* idx, const float* w, const float* x, int64_t ld_x, int64_t F_in,
+                             const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
+                             float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
+                             kgx_stream_t stream_) {
+  kgx_fused_args a{};  // (zeroed: one table, no slice)
+  a.struct_size = sizeof(a);
+  a.reduce = reduce; a.flags = flags;
+  a.work = kgx_work{rowptr, rows, n_rows, items, n_items, n_items, n_items, nullptr, nullptr, 0, split, n_split, idx, w};
+  a.x = x; a.ld_x = ld_x; a.F_in = F_in;
+  a.W = W; a.F_out = F_out; a.bias = bias; a.gin_scale = gin_scale;
+  a.out = out; a.ld_out = ld_out; a.partials = partials;
+  a.agg_out = agg_out; a.ld_agg = ld_agg;
+  return kgx_spmm_gemm_run(&a, stream_);
 }

@@ -75,7 +75,7 @@ struct F256Args {
   int accumulate;
   int relu;
   float gin_scale;
-  // two-table gathers (kgx_spmm_gemm_f256_ex): source columns c >= n_x1 are rows
+  // two-table gathers (kgx_fused_args.x2): source columns c >= n_x1 are rows
   // c - n_x1 of a second table x2 (same ld_x); x2b = x2 - n_x1 * ld_x (host
   // address math), so a gather's address is one select of the base
   const float* x2b;
@@ -713,85 +713,87 @@ int launch256(const F256Args& a, hipStream_t s) {
 
 using namespace kgx;
 
-extern "C" int kgx_spmm_gemm_f256_ex(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                     const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                                     const int32_t* tiny_pack, const float* tiny_w, const int32_t* split,
-                                     int64_t n_split, const int32_t* idx, const float* w, const float* x,
-                                     int64_t ld_x, const float* x2, int64_t n_x1, int64_t F_in, const float* W,
-                                     int64_t F_out, const float* bias, int flags, float gin_scale, float* out,
-                                     int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                                     kgx_stream_t stream_) {
+extern "C" int kgx_spmm_gemm_f256_run(const kgx_fused_args* p, kgx_stream_t stream_) {
+  KGX_REQUIRE(p, KGX_ERR_ARG, "kgx_spmm_gemm_f256: the kgx_fused_args pointer is NULL");
+  KGX_REQUIRE(p->struct_size == sizeof(*p), KGX_ERR_ARG,
+              "kgx_spmm_gemm_f256: struct_size %llu is not sizeof(kgx_fused_args) = %zu (a binding of another "
+              "kgx.h?)", (unsigned long long)p->struct_size, sizeof(*p));
+  KGX_REQUIRE(p->slice.n_classes == 0, KGX_ERR_ARG,
+              "kgx_spmm_gemm_f256: slice.n_classes must be 0 (the 256-wide kernels have no sliced schedule)");
+  const kgx_work& g = p->work;
   hipStream_t stream = as_stream(stream_);
-  KGX_REQUIRE(reduce >= KGX_SUM && reduce <= KGX_MIN, KGX_ERR_ARG, "kgx_spmm_gemm_f256: reduce %d unsupported",
-              reduce);
-  KGX_REQUIRE(F_in == kF, KGX_ERR_UNSUPPORTED, "kgx_spmm_gemm_f256: F_in must be %d (got %lld)", kF,
-              (long long)F_in);
-  KGX_REQUIRE(F_out > 0 && F_out <= kF && F_out % 16 == 0, KGX_ERR_UNSUPPORTED,
-              "kgx_spmm_gemm_f256: F_out must be a multiple of 16 <= 256 (got %lld)", (long long)F_out);
-  KGX_REQUIRE(n_rows >= 0 && n_items >= 0 && n_split >= 0, KGX_ERR_ARG, "kgx_spmm_gemm_f256: negative size");
-  KGX_REQUIRE(!items || tiny_pack || n_short_end == n_items, KGX_ERR_ARG,
+  KGX_REQUIRE(p->reduce >= KGX_SUM && p->reduce <= KGX_MIN, KGX_ERR_ARG, "kgx_spmm_gemm_f256: reduce %d unsupported",
+              p->reduce);
+  KGX_REQUIRE(p->F_in == kF, KGX_ERR_UNSUPPORTED, "kgx_spmm_gemm_f256: F_in must be %d (got %lld)", kF,
+              (long long)p->F_in);
+  KGX_REQUIRE(p->F_out > 0 && p->F_out <= kF && p->F_out % 16 == 0, KGX_ERR_UNSUPPORTED,
+              "kgx_spmm_gemm_f256: F_out must be a multiple of 16 <= 256 (got %lld)", (long long)p->F_out);
+  KGX_REQUIRE(g.n_rows >= 0 && g.n_items >= 0 && g.n_split >= 0, KGX_ERR_ARG, "kgx_spmm_gemm_f256: negative size");
+  KGX_REQUIRE(!g.items || g.tiny_pack || g.n_short_end == g.n_items, KGX_ERR_ARG,
               "kgx_spmm_gemm_f256: without tiny_pack, n_short_end must equal n_items");
-  KGX_REQUIRE(!tiny_pack || (items && n_short_end >= 0 && n_short_end <= n_items && (w == nullptr || tiny_w)),
+  KGX_REQUIRE(!g.tiny_pack || (g.items && g.n_short_end >= 0 && g.n_short_end <= g.n_items &&
+                               (g.w == nullptr || g.tiny_w)),
               KGX_ERR_ARG, "kgx_spmm_gemm_f256: the tiny-row records need the schedule, 0 <= n_short_end <= n_items "
               "(and weights when weighted)");
-  KGX_REQUIRE((flags & ~(KGX_FUSED_PRE_GIN | KGX_FUSED_ACCUMULATE | KGX_FUSED_SHARE_GPU | KGX_FUSED_RELU |
+  KGX_REQUIRE((p->flags & ~(KGX_FUSED_PRE_GIN | KGX_FUSED_ACCUMULATE | KGX_FUSED_SHARE_GPU | KGX_FUSED_RELU |
                          KGX_FUSED_CU_SPLIT)) == 0,
-              KGX_ERR_ARG, "kgx_spmm_gemm_f256: unknown flags 0x%x", flags);
-  KGX_REQUIRE(!((flags & KGX_FUSED_RELU) && (flags & KGX_FUSED_ACCUMULATE)), KGX_ERR_ARG,
+              KGX_ERR_ARG, "kgx_spmm_gemm_f256: unknown flags 0x%x", p->flags);
+  KGX_REQUIRE(!((p->flags & KGX_FUSED_RELU) && (p->flags & KGX_FUSED_ACCUMULATE)), KGX_ERR_ARG,
               "kgx_spmm_gemm_f256: KGX_FUSED_RELU cannot be combined with KGX_FUSED_ACCUMULATE");
-  KGX_REQUIRE(!agg_out || (ld_agg >= F_in && reinterpret_cast<uintptr_t>(agg_out) % 16 == 0 && ld_agg % 4 == 0),
+  KGX_REQUIRE(!p->agg_out || (p->ld_agg >= p->F_in && reinterpret_cast<uintptr_t>(p->agg_out) % 16 == 0 &&
+                              p->ld_agg % 4 == 0),
               KGX_ERR_ARG, "kgx_spmm_gemm_f256: agg_out must be 16-byte aligned with ld >= F_in, ld %% 4 == 0");
-  KGX_REQUIRE(!x2 || (n_x1 >= 0 && n_x1 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(x2) % 16 == 0),
+  KGX_REQUIRE(!p->x2 || (p->n_x1 >= 0 && p->n_x1 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(p->x2) % 16 == 0),
               KGX_ERR_ARG, "kgx_spmm_gemm_f256: x2 must be 16-byte aligned and 0 <= n_x1 < 2^31");
-  KGX_REQUIRE(!x2 || reduce == KGX_SUM, KGX_ERR_UNSUPPORTED,
+  KGX_REQUIRE(!p->x2 || p->reduce == KGX_SUM, KGX_ERR_UNSUPPORTED,
               "kgx_spmm_gemm_f256: two-table gathers are implemented for the sum");
-  if (n_rows == 0) return KGX_OK;
-  KGX_REQUIRE(rowptr && rows && idx && x && W && out, KGX_ERR_ARG, "kgx_spmm_gemm_f256: null pointer");
-  KGX_REQUIRE(ld_x < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_spmm_gemm_f256: x leading dimension >= 2^31");
-  KGX_REQUIRE(ld_x % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, KGX_ERR_ARG,
+  if (g.n_rows == 0) return KGX_OK;
+  KGX_REQUIRE(g.rowptr && g.rows && g.idx && p->x && p->W && p->out, KGX_ERR_ARG, "kgx_spmm_gemm_f256: null pointer");
+  KGX_REQUIRE(p->ld_x < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_spmm_gemm_f256: x leading dimension >= 2^31");
+  KGX_REQUIRE(p->ld_x % 4 == 0 && reinterpret_cast<uintptr_t>(p->x) % 16 == 0, KGX_ERR_ARG,
               "kgx_spmm_gemm_f256: x must be 16-byte aligned with ld %% 4 == 0");
-  KGX_REQUIRE(ld_out >= F_out && ld_out % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0, KGX_ERR_ARG,
+  KGX_REQUIRE(p->ld_out >= p->F_out && p->ld_out % 4 == 0 && reinterpret_cast<uintptr_t>(p->out) % 16 == 0, KGX_ERR_ARG,
               "kgx_spmm_gemm_f256: out must be 16-byte aligned with ld >= F_out, ld %% 4 == 0");
-  KGX_REQUIRE(!items || n_split == 0 || (split && partials), KGX_ERR_ARG,
+  KGX_REQUIRE(!g.items || g.n_split == 0 || (g.split && p->partials), KGX_ERR_ARG,
               "kgx_spmm_gemm_f256: split rows need split list and partials");
   F256Args a{};
-  a.rowptr = rowptr;
-  a.rows = rows;
-  a.n_rows = n_rows;
-  a.items = reinterpret_cast<const int4*>(items);
-  a.n_items = items ? n_items : 0;
-  a.n_work = items ? (tiny_pack ? n_short_end : n_items) : 0;
-  a.n_long = items ? n_long_items : -1;
-  a.tpack = items ? reinterpret_cast<const int4*>(tiny_pack) : nullptr;
-  a.tw = reinterpret_cast<const float2*>(tiny_w);
-  a.n_tiny = (items && tiny_pack) ? n_items - n_short_end : 0;
-  a.split = reinterpret_cast<const int4*>(split);
-  a.n_split = items ? n_split : 0;
-  a.idx = idx;
-  a.w = w;
-  a.x = x;
-  a.ld_x = ld_x;
-  a.W = W;
-  a.F_out = int(F_out);
-  a.bias = bias;
-  a.out = out;
-  a.ld_o = ld_out;
-  a.partials = partials;
-  a.agg_out = agg_out;
-  a.ld_agg = ld_agg;
-  a.pre_gin = (flags & KGX_FUSED_PRE_GIN) != 0;
-  a.accumulate = (flags & KGX_FUSED_ACCUMULATE) != 0;
-  a.relu = (flags & KGX_FUSED_RELU) != 0;
-  a.gin_scale = gin_scale;
-  a.cu_split = (flags & KGX_FUSED_CU_SPLIT) != 0;
-  a.n_x1 = x2 ? int32_t(n_x1) : INT32_MAX;
+  a.rowptr = g.rowptr;
+  a.rows = g.rows;
+  a.n_rows = g.n_rows;
+  a.items = reinterpret_cast<const int4*>(g.items);
+  a.n_items = g.items ? g.n_items : 0;
+  a.n_work = g.items ? (g.tiny_pack ? g.n_short_end : g.n_items) : 0;
+  a.n_long = g.items ? g.n_long_items : -1;
+  a.tpack = g.items ? reinterpret_cast<const int4*>(g.tiny_pack) : nullptr;
+  a.tw = reinterpret_cast<const float2*>(g.tiny_w);
+  a.n_tiny = (g.items && g.tiny_pack) ? g.n_items - g.n_short_end : 0;
+  a.split = reinterpret_cast<const int4*>(g.split);
+  a.n_split = g.items ? g.n_split : 0;
+  a.idx = g.idx;
+  a.w = g.w;
+  a.x = p->x;
+  a.ld_x = p->ld_x;
+  a.W = p->W;
+  a.F_out = int(p->F_out);
+  a.bias = p->bias;
+  a.out = p->out;
+  a.ld_o = p->ld_out;
+  a.partials = p->partials;
+  a.agg_out = p->agg_out;
+  a.ld_agg = p->ld_agg;
+  a.pre_gin = (p->flags & KGX_FUSED_PRE_GIN) != 0;
+  a.accumulate = (p->flags & KGX_FUSED_ACCUMULATE) != 0;
+  a.relu = (p->flags & KGX_FUSED_RELU) != 0;
+  a.gin_scale = p->gin_scale;
+  a.cu_split = (p->flags & KGX_FUSED_CU_SPLIT) != 0;
+  a.n_x1 = p->x2 ? int32_t(p->n_x1) : INT32_MAX;
   // x2 - n_x1 * ld_x as an address (modular): gather_src adds row_off(c) for c >= n_x1
-  a.x2b = x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(x2) -
-                                               uintptr_t(n_x1) * uintptr_t(ld_x) * sizeof(float))
+  a.x2b = p->x2 ? reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(p->x2) -
+                                               uintptr_t(p->n_x1) * uintptr_t(p->ld_x) * sizeof(float))
              : nullptr;
-  const bool wt = w != nullptr;
-  if (x2) return wt ? launch256<KGX_SUM, true, true>(a, stream) : launch256<KGX_SUM, false, true>(a, stream);
-  switch (reduce) {
+  const bool wt = g.w != nullptr;
+  if (p->x2) return wt ? launch256<KGX_SUM, true, true>(a, stream) : launch256<KGX_SUM, false, true>(a, stream);
+  switch (p->reduce) {
     case KGX_SUM: return wt ? launch256<KGX_SUM, true, false>(a, stream) : launch256<KGX_SUM, false, false>(a, stream);
     case KGX_MEAN: return wt ? launch256<KGX_MEAN, true, false>(a, stream) : launch256<KGX_MEAN, false, false>(a, stream);
     case KGX_MAX: return wt ? launch256<KGX_MAX, true, false>(a, stream) : launch256<KGX_MAX, false, false>(a, stream);
@@ -799,14 +801,3 @@ extern "C" int kgx_spmm_gemm_f256_ex(int reduce, const int32_t* rowptr, const in
   }
 }
 
-extern "C" int kgx_spmm_gemm_f256(int reduce, const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
-                                  const int32_t* items, int64_t n_items, int64_t n_long_items, int64_t n_short_end,
-                                  const int32_t* tiny_pack, const float* tiny_w, const int32_t* split, int64_t n_split,
-                                  const int32_t* idx, const float* w, const float* x, int64_t ld_x, int64_t F_in,
-                                  const float* W, int64_t F_out, const float* bias, int flags, float gin_scale,
-                                  float* out, int64_t ld_out, float* partials, float* agg_out, int64_t ld_agg,
-                                  kgx_stream_t stream) {
-  return kgx_spmm_gemm_f256_ex(reduce, rowptr, rows, n_rows, items, n_items, n_long_items, n_short_end, tiny_pack,
-                               tiny_w, split, n_split, idx, w, x, ld_x, nullptr, 0, F_in, W, F_out, bias, flags,
-                               gin_scale, out, ld_out, partials, agg_out, ld_agg, stream);
-}

@@ -36,6 +36,47 @@ _i32p = ctypes.c_void_p
 _f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
+_f32 = ctypes.c_float
+
+
+# Mirrors of the argument structs of include/kgx.h: the same field names in the same order
+# (tests/test_abi_layout_host.py holds offsets and sizes equal to the header's).
+class Work(ctypes.Structure):
+    _fields_ = [
+        ("rowptr", _i32p), ("rows", _i32p), ("n_rows", _i64),
+        ("items", _i32p), ("n_items", _i64), ("n_long_items", _i64), ("n_short_end", _i64),
+        ("tiny_pack", _i32p), ("tiny_w", _f32p), ("n_tiny_deg2", _i64),
+        ("split", _i32p), ("n_split", _i64), ("idx", _i32p), ("w", _f32p),
+    ]
+
+
+class Slice(ctypes.Structure):
+    _fields_ = [
+        ("items", _i32p), ("lists", _i32p), ("n_classes", _i64), ("tiles", _i64),
+        ("idx", _i32p), ("w", _f32p), ("split", _i32p), ("n_split", _i64),
+        ("head_short_end", _i64),
+    ]
+
+
+class SpmmArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64), ("reduce", ctypes.c_int32), ("epilogue", ctypes.c_int32), ("work", Work),
+        ("table", _f32p), ("ld_table", _i64), ("table2", _f32p), ("n_table1", _i64), ("F", _i64),
+        ("out", _f32p), ("ld_out", _i64), ("bias", _f32p), ("xroot", _f32p), ("ld_x", _i64),
+        ("gin_scale", _f32), ("drop_p", _f32), ("drop_key", _i32p), ("drop_seed", ctypes.c_uint64),
+        ("partials", _f32p), ("counters", _i32p),
+    ]
+
+
+class FusedArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64), ("reduce", ctypes.c_int32), ("flags", ctypes.c_int32), ("work", Work),
+        ("x", _f32p), ("ld_x", _i64), ("x2", _f32p), ("n_x1", _i64), ("F_in", _i64),
+        ("W", _f32p), ("F_out", _i64), ("bias", _f32p), ("gin_scale", _f32), ("pad_", _f32),
+        ("out", _f32p), ("ld_out", _i64), ("partials", _f32p), ("agg_out", _f32p), ("ld_agg", _i64),
+        ("slice", Slice),
+    ]
+
 
 # name -> argtypes (every entry point returns int unless listed in _RESTYPES)
 _SIGNATURES = {
@@ -75,16 +116,9 @@ _SIGNATURES = {
         _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64,
         _f32p, _f32p, _i64, ctypes.c_float, _i32p, ctypes.c_float, ctypes.c_uint64, _f32p, ctypes.c_void_p,
     ],
-    "kgx_spmm_ex": [
-        _int, _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64,
-        _f32p, _f32p, _i64, ctypes.c_float, _i32p, ctypes.c_float, ctypes.c_uint64, _f32p, ctypes.c_void_p,
-    ],
-    "kgx_spmm_ex2": [
-        _int, _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64,
-        _f32p, _f32p, _i64, ctypes.c_float, _i32p, ctypes.c_float, ctypes.c_uint64, _f32p, _i32p, ctypes.c_void_p,
-    ],
+    "kgx_spmm_run": [ctypes.POINTER(SpmmArgs), ctypes.c_void_p],
+    "kgx_spmm_gemm_run": [ctypes.POINTER(FusedArgs), ctypes.c_void_p],
+    "kgx_spmm_gemm_f256_run": [ctypes.POINTER(FusedArgs), ctypes.c_void_p],
     "kgx_multi_aggr": [
         _int, ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
         _i32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, ctypes.c_void_p,
@@ -96,37 +130,6 @@ _SIGNATURES = {
         _int, _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
         _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
         _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_ex": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_ex2": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_f256": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_f256_ex": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_ex3": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64, ctypes.c_void_p,
-    ],
-    "kgx_spmm_gemm_ex4": [
-        _int, _i32p, _i32p, _i64, _i32p, _i64, _i64, _i64, _i32p, _f32p, _i64, _i32p, _i64,
-        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _f32p, _i64, _f32p, _int, ctypes.c_float,
-        _f32p, _i64, _f32p, _f32p, _i64,
-        _i32p, _i32p, _int, _i64, _i32p, _f32p, _i32p, _i64, _i64, ctypes.c_void_p,
     ],
     "kgx_slice_class": [ctypes.c_int32, _int],
     "kgx_slice_grid": [_i64, _i64, _int],
@@ -290,6 +293,26 @@ def require_device(*tensors: torch.Tensor | None) -> torch.device:
 
 def ptr(t: torch.Tensor | None) -> ctypes.c_void_p | None:
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def addr(t: torch.Tensor | None) -> int | None:
+    """A tensor's device address as a struct's pointer field takes it (None: NULL)."""
+    return None if t is None else t.data_ptr()
+
+
+def work(rowptr, rows, items, split, idx, w, n_long, n_short_end=None, tpack=None, tw=None, n_tiny2=0) -> Work:
+    """The kgx_work of one launch: the CSR, its schedule lists (items / split, None
+    when absent) and the packed degree <= 2 tail from n_short_end on (None: no
+    tail).  It holds addresses only: the caller keeps the tensors until the call returns."""
+    n_items = 0 if items is None else items.shape[0]
+    return Work(
+        rowptr=addr(rowptr), rows=addr(rows), n_rows=rowptr.numel() - 1,
+        items=addr(items), n_items=n_items, n_long_items=n_long,
+        n_short_end=n_items if n_short_end is None else n_short_end,
+        tiny_pack=addr(tpack), tiny_w=addr(tw), n_tiny_deg2=n_tiny2,
+        split=addr(split), n_split=0 if split is None else split.shape[0],
+        idx=addr(idx), w=addr(w),
+    )
 
 
 def stream(device: torch.device) -> ctypes.c_void_p:

@@ -973,7 +973,7 @@ class ShardedGraph:
         H -- it writes them, while the exchange is in flight.  g_b: for the rows
         in H, their own-source edges followed by their first-group edges
         (sources >= n_local index the halo buffer), written once by ONE
-        two-table pass (kgx_spmm_gemm_ex3 / kgx_spmm_ex2) instead of an own pass
+        two-table pass (x2 of the fused op / table2 of the gather-reduce) instead of an own pass
         that writes them and a halo pass that reads and rewrites them.  later:
         [(step to wait for, CSR, halo lo, halo hi)] for the remaining groups,
         accumulate-only over the rows each touches.  Each row's sum is own

@@ -69,7 +69,7 @@ class CSRGraph:
     split_len: int = 0
     # items [n_long, n_items): the schedule's suffix of unsplit rows of degree <=
     # KGX_SHORT_ROW_MAX, which the fused kernel reduces 32-64 rows per block
-    # iteration (kgx_spmm_gemm_ex); -1: none / not computed
+    # iteration (kgx_work.n_long_items); -1: none / not computed
     n_long: int = -1
     extras: dict = field(default_factory=dict)
 

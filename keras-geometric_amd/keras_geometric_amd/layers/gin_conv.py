@@ -7,7 +7,7 @@ reference's edge order and applies the (1+eps)*x_i + aggr epilogue; the MLP's
 Dense layers run on kgx_dense (bf16x3-split MFMA, f32-accurate; the library
 fp32 GEMM only past its K/N <= 256 shapes).  When the MLP's first Dense fits a
 fused kernel (F_in 128 -> <= 128 units: kgx_spmm_gemm; F_in 256 -> 256 units,
-BASELINE config C4: kgx_spmm_gemm_f256; bias, none/ReLU), that Dense runs in the
+BASELINE config C4: kgx_spmm_gemm_f256_run; bias, none/ReLU), that Dense runs in the
 aggregation's epilogue on MFMA too (KGX_FUSED_PRE_GIN), so the [N, F_in]
 aggregate is never written; EXACT mode keeps the separate, bit-exact aggregation.
 """

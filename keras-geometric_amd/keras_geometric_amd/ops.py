@@ -37,6 +37,28 @@ def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 _EXACT_DYN = __import__("os").environ.get("KGX_EXACT_DYN", "1") != "0"
 
 
+def _spmm_launch(out, reduce, epilogue, table, table2, rowptr, rows, items, split, idx, w, n_slots, n_long, bias,
+                 xroot, gin_scale, counters=None, drop_key=None, drop_p=0.0, drop_seed=0):
+    """One kgx_spmm_run into out [n_dst > 0, F > 0]: the split rows' partials and
+    the kgx_spmm_args by field name (table2: sources >= table.shape[0] are its rows)."""
+    F = table.shape[1]
+    partials = None
+    if items is not None and split is not None and split.shape[0] > 0 and reduce != nat.STD:
+        partials = torch.empty((n_slots, F), dtype=torch.float32, device=out.device)
+    a = nat.SpmmArgs(
+        struct_size=ctypes.sizeof(nat.SpmmArgs), reduce=reduce, epilogue=epilogue,
+        work=nat.work(rowptr, rows, items, split, idx, w, n_long),
+        table=nat.addr(table), ld_table=table.stride(0), table2=nat.addr(table2),
+        n_table1=table.shape[0] if table2 is not None else 0, F=F,
+        out=nat.addr(out), ld_out=out.stride(0),
+        bias=nat.addr(bias), xroot=nat.addr(xroot), ld_x=xroot.stride(0) if xroot is not None else 0,
+        gin_scale=float(gin_scale), drop_p=float(drop_p),
+        drop_key=nat.addr(drop_key) if drop_p > 0 else None, drop_seed=int(drop_seed) & (2**64 - 1),
+        partials=nat.addr(partials), counters=nat.addr(counters),
+    )
+    nat.check(nat.lib().kgx_spmm_run(ctypes.byref(a), nat.stream(out.device)), "kgx_spmm")
+
+
 @torch.library.custom_op("kgx::spmm", mutates_args=())
 def spmm(
     table: torch.Tensor,
@@ -65,28 +87,13 @@ def spmm(
     out = torch.empty((n_dst, F), dtype=torch.float32, device=dev)
     if n_dst == 0 or F == 0:
         return out
-    n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    partials = None
-    if items is not None and n_split > 0 and reduce != nat.STD:
-        partials = torch.empty((n_slots, F), dtype=torch.float32, device=dev)
     if items is not None:  # EXACT mode (no items): n_long names the short suffix of the row list (or -1)
-        n_long = n_items if n_long < 0 or n_long > n_items else n_long
+        n_long = items.shape[0] if n_long < 0 or n_long > items.shape[0] else n_long
     # EXACT mode: the hub-row kernel hands its items out dynamically (KGX_EXACT_DYN=0: static, A/B only)
     counters = (torch.zeros(2, dtype=torch.int32, device=dev)
                 if items is None and reduce != nat.STD and _EXACT_DYN else None)
-    nat.check(
-        nat.lib().kgx_spmm_ex2(
-            reduce, epilogue, nat.ptr(rowptr), nat.ptr(rows), n_dst,
-            nat.ptr(items), n_items, n_long, nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(table), table.stride(0), None, 0, F,
-            nat.ptr(out), out.stride(0),
-            nat.ptr(bias), nat.ptr(xroot), xroot.stride(0) if xroot is not None else 0, float(gin_scale),
-            nat.ptr(drop_key) if drop_p > 0 else None, float(drop_p), int(drop_seed) & (2**64 - 1),
-            nat.ptr(partials), nat.ptr(counters), nat.stream(dev),
-        ),
-        "kgx_spmm",
-    )
+    _spmm_launch(out, reduce, epilogue, table, None, rowptr, rows, items, split, idx, w, n_slots, n_long, bias, xroot,
+                 gin_scale, counters, drop_key, drop_p, drop_seed)
     return out
 
 
@@ -117,9 +124,9 @@ def spmm_acc_(
     """out[i] += SUM_{e in row i} table[idx[e]] (* w[e]) in place (KGX_EPI_ACCUM,
     the default epilogue); any other epilogue overwrites the scheduled rows of
     out (and leaves the rest untouched).  table2: sources >= table.shape[0]
-    are rows of table2 (kgx_spmm_ex2)."""
+    are rows of table2 (two-table gathers, kgx_spmm_args.table2)."""
     table, w, bias, xroot, table2 = _f32c(table), _f32c(w), _f32c(bias), _f32c(xroot), _f32c(table2)
-    dev = nat.require_device(out, table, rowptr, rows, idx, w, items, split, bias, xroot, table2)
+    nat.require_device(out, table, rowptr, rows, idx, w, items, split, bias, xroot, table2)
     if table2 is not None and (table2.dim() != 2 or table2.shape[1] != table.shape[1]
                                or (table2.shape[0] and table2.stride(0) != table.stride(0))):
         raise ValueError("spmm_acc_: table2 must have table's row width and leading dimension")
@@ -130,22 +137,9 @@ def spmm_acc_(
     if n_dst == 0 or F == 0:
         return
     n_items = 0 if items is None else items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
-    partials = None
-    if items is not None and n_split > 0:
-        partials = torch.empty((n_slots, F), dtype=torch.float32, device=dev)
     n_long = n_items if n_long < 0 or n_long > n_items else n_long
-    nat.check(
-        nat.lib().kgx_spmm_ex2(
-            nat.SUM, int(epilogue), nat.ptr(rowptr), nat.ptr(rows), n_dst,
-            nat.ptr(items), n_items, n_long, nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(table), table.stride(0), nat.ptr(table2),
-            table.shape[0] if table2 is not None else 0, F,
-            nat.ptr(out), out.stride(0), nat.ptr(bias), nat.ptr(xroot), xroot.stride(0) if xroot is not None else 0,
-            float(gin_scale), None, 0.0, 0, nat.ptr(partials), None, nat.stream(dev),
-        ),
-        "kgx_spmm",
-    )
+    _spmm_launch(out, nat.SUM, int(epilogue), table, table2, rowptr, rows, items, split, idx, w, n_slots, n_long, bias,
+                 xroot, gin_scale)
 
 
 @spmm_acc_.register_fake
@@ -215,7 +209,7 @@ class _unsplit:
 
 
 def _tiny_abi(items, n_items, n_long, tpack, tw, n_short_end, n_tiny2):
-    """(n_short_end, tpack, tw, n_tiny2) arguments of kgx_spmm_gemm_ex2."""
+    """(n_short_end, tiny_pack, tiny_w, n_tiny_deg2) of a fused launch's kgx_work."""
     if items is None or tpack is None or not (n_long <= n_short_end <= n_items):
         return n_items, None, None, 0
     from . import tiny
@@ -226,40 +220,37 @@ def _tiny_abi(items, n_items, n_long, tpack, tw, n_short_end, n_tiny2):
     return n_short_end, tpack, tw, n_tiny2
 
 
-def _x2_args(x, x2):
-    """(x2 pointer, n_x1) of kgx_spmm_gemm_ex3: sources >= x.shape[0] are rows of x2."""
-    if x2 is None:
-        return None, 0
-    if x2.dim() != 2 or x2.shape[1] != x.shape[1] or (x2.shape[0] and x2.stride(0) != x.stride(0)):
-        raise ValueError(f"spmm_gemm: x2 {tuple(x2.shape)} must have x's row width and leading dimension")
-    return nat.ptr(x2), x.shape[0]
-
-
-F256 = 256  # F_in of kgx_spmm_gemm_f256 (GINConv C4: 256 -> 256)
+F256 = 256  # F_in of kgx_spmm_gemm_f256_run (GINConv C4: 256 -> 256)
 # layers take the 256-wide fused kernels by default: at C4 they beat the unfused
 # pair (kgx_spmm + kgx_dense), 22.0 vs 24.5 ms (DESIGN.md §4); KGX_FUSED256=0 turns them off
 _F256_DEFAULT = "1"
 
 
-def _f256_call(reduce, rowptr, rows, n_dst, items, n_items, split, n_split, idx, w, x, x2, W, bias, flags, gin_scale,
-               out, partials, agg, dev, tpack=None, tw=None, n_short_end=-1, n_long=-1):
-    """kgx_spmm_gemm_f256_ex: the 256-wide fused kernels (main + the degree <= 2
-    tail from the packed records); x2: second feature table for sources >=
-    x.shape[0] (the sharded GIN layer's merged halo pass; sum only)."""
-    n_se, tpack, tw, _ = _tiny_abi(items, n_items, 0, tpack, tw if w is not None else None, n_short_end, 0)
-    x2p, n_x1 = _x2_args(x, x2)
-    nat.check(
-        nat.lib().kgx_spmm_gemm_f256_ex(
-            reduce, nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items,
-            n_long if items is not None and 0 <= n_long <= n_se else -1, n_se, nat.ptr(tpack), nat.ptr(tw),
-            nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), W.shape[1],
-            nat.ptr(bias),
-            flags, float(gin_scale), nat.ptr(out), out.stride(0), nat.ptr(partials),
-            nat.ptr(agg), agg.stride(0) if agg is not None else 0, nat.stream(dev),
-        ),
-        "kgx_spmm_gemm_f256",
+def _fused_args(reduce, flags, work, x, x2, W, bias, gin_scale, out, partials, agg) -> nat.FusedArgs:
+    """The kgx_fused_args of one launch, unsliced; x2: second feature table for
+    sources >= x.shape[0] (the sharded layers' merged halo passes; sums only)."""
+    if x2 is not None and (x2.dim() != 2 or x2.shape[1] != x.shape[1]
+                           or (x2.shape[0] and x2.stride(0) != x.stride(0))):
+        raise ValueError(f"spmm_gemm: x2 {tuple(x2.shape)} must have x's row width and leading dimension")
+    return nat.FusedArgs(
+        struct_size=ctypes.sizeof(nat.FusedArgs), reduce=reduce, flags=flags, work=work,
+        x=nat.addr(x), ld_x=x.stride(0), x2=nat.addr(x2), n_x1=x.shape[0] if x2 is not None else 0, F_in=x.shape[1],
+        W=nat.addr(W), F_out=W.shape[1], bias=nat.addr(bias), gin_scale=float(gin_scale),
+        out=nat.addr(out), ld_out=out.stride(0), partials=nat.addr(partials),
+        agg_out=nat.addr(agg), ld_agg=agg.stride(0) if agg is not None else 0,
     )
+
+
+def _f256_call(reduce, rowptr, rows, items, split, idx, w, x, x2, W, bias, flags, gin_scale, out, partials, agg,
+               tpack=None, tw=None, n_short_end=-1, n_long=-1):
+    """kgx_spmm_gemm_f256_run: the 256-wide fused kernels (main + the degree <= 2
+    tail from the packed records), never sliced."""
+    n_items = 0 if items is None else items.shape[0]
+    n_se, tpack, tw, _ = _tiny_abi(items, n_items, 0, tpack, tw if w is not None else None, n_short_end, 0)
+    work = nat.work(rowptr, rows, items, split, idx, w, n_long if items is not None and 0 <= n_long <= n_se else -1,
+                    n_se, tpack, tw)
+    a = _fused_args(reduce, flags, work, x, x2, W, bias, gin_scale, out, partials, agg)
+    nat.check(nat.lib().kgx_spmm_gemm_f256_run(ctypes.byref(a), nat.stream(out.device)), "kgx_spmm_gemm_f256")
 
 
 def _f256_cu_split(n_edges: int, n_tiny: int) -> bool:
@@ -362,8 +353,7 @@ def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, 
     allow_split is off for the training forward's saved-aggregate launch: its
     tail launches also store the aggregated rows (the EXTRA instantiations), and
     split it measured slower (NS training step 23.1 -> 25.0 ms, profiles/r05/train/).
-    sl: a slice.SlicedSchedule for the main kernel (kgx_spmm_gemm_ex4), or None."""
-    n_dst = rowptr.numel() - 1
+    sl: a slice.SlicedSchedule for the main kernel (kgx_fused_args.slice), or None."""
     n_items = 0 if items is None else items.shape[0]
     n_split = 0 if split is None else split.shape[0]
     if sl is not None and (items is None or x.shape[1] == F256 or x2 is not None):
@@ -379,8 +369,8 @@ def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, 
                 _f256_cu_split(idx.numel(), n_items - (n_short_end if n_short_end >= 0 else n_items)):
             flags |= nat.FUSED_CU_SPLIT
             _count_cu_split()
-        _f256_call(reduce, rowptr, rows, n_dst, items, n_items, split, n_split, idx, w, x, x2, W, bias, flags,
-                   gin_scale, out, partials, agg, dev, tpack, tw, n_short_end, n_long)
+        _f256_call(reduce, rowptr, rows, items, split, idx, w, x, x2, W, bias, flags, gin_scale, out, partials, agg,
+                   tpack, tw, n_short_end, n_long)
         return
     n_long = n_items if n_long < 0 or n_long > n_items else n_long
     n_se, tpack, tw, n_tiny2 = _tiny_abi(items, n_items, n_long, tpack, tw if w is not None else None, n_short_end,
@@ -388,22 +378,17 @@ def _fused_launch(out, agg, x, x2, rowptr, rows, items, split, idx, w, n_slots, 
     if allow_split and _split_allowed(dev) and _fused_cu_split(idx.numel(), n_items - n_long):
         flags |= nat.FUSED_CU_SPLIT
         _count_cu_split()
-    x2p, n_x1 = _x2_args(x, x2)
     if sl is not None and ((w is not None) != (sl.w is not None) or sl.n_long != n_long):
         sl = None  # (lists built without weights, or for another long-item boundary)
-    sl_args = (None, None, 0, 0, None, None, None, 0, -1) if sl is None else (
-        nat.ptr(sl.items), nat.ptr(sl.lists), sl.C, sl.tiles, nat.ptr(sl.col), nat.ptr(sl.w), nat.ptr(sl.fix),
-        sl.n_rows, min(sl.head_short_end, n_se))
-    nat.check(
-        nat.lib().kgx_spmm_gemm_ex4(
-            reduce, nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, n_long, n_se, nat.ptr(tpack),
-            nat.ptr(tw), n_tiny2, nat.ptr(split), n_split,
-            nat.ptr(idx), nat.ptr(w), nat.ptr(x), x.stride(0), x2p, n_x1, x.shape[1], nat.ptr(W), W.shape[1],
-            nat.ptr(bias), flags, float(gin_scale), nat.ptr(out), out.stride(0), nat.ptr(partials),
-            nat.ptr(agg), agg.stride(0) if agg is not None else 0, *sl_args, nat.stream(dev),
-        ),
-        "kgx_spmm_gemm",
-    )
+    a = _fused_args(reduce, flags, nat.work(rowptr, rows, items, split, idx, w, n_long, n_se, tpack, tw, n_tiny2),
+                    x, x2, W, bias, gin_scale, out, partials, agg)
+    if sl is not None:
+        a.slice = nat.Slice(
+            items=nat.addr(sl.items), lists=nat.addr(sl.lists), n_classes=sl.C, tiles=sl.tiles,
+            idx=nat.addr(sl.col), w=nat.addr(sl.w), split=nat.addr(sl.fix), n_split=sl.n_rows,
+            head_short_end=min(sl.head_short_end, n_se),
+        )
+    nat.check(nat.lib().kgx_spmm_gemm_run(ctypes.byref(a), nat.stream(dev)), "kgx_spmm_gemm")
 
 
 def _spmm_gemm_impl(x, rowptr, rows, items, split, idx, w, n_slots, reduce, W, bias, pre_gin, gin_scale, save_agg,
@@ -452,8 +437,8 @@ def spmm_gemm(
     sl_max_list: int = 0,
     sl_head_short_end: int = -1,
 ) -> torch.Tensor:
-    """x2 (two-table gathers, kgx_spmm_gemm_ex3): sources >= x.shape[0] are rows of x2.
-    sl_*: a sliced schedule for the main kernel (slice.SlicedSchedule's arrays, kgx_spmm_gemm_ex4)."""
+    """x2 (two-table gathers): sources >= x.shape[0] are rows of x2.
+    sl_*: a sliced schedule for the main kernel (slice.SlicedSchedule's arrays, kgx_fused_args.slice)."""
     sl = None
     if sl_items is not None:
         from .slice import SlicedSchedule
@@ -554,7 +539,7 @@ def _spmm_gemm_acc_fake(out, x, rowptr, rows, items, split, idx, w, n_slots, red
 
 
 def fused_transform_supported(f_in: int, f_out: int, two_table: bool = False) -> bool:
-    """Shapes kgx_spmm_gemm (F_in 128) and kgx_spmm_gemm_f256 (F_in 256)
+    """Shapes kgx_spmm_gemm (F_in 128) and kgx_spmm_gemm_f256_run (F_in 256)
     implement, with one feature table or two (two_table: the sharded layers'
     merged halo passes, sum only; aggregate-then-transform is also only worth
     it when F_in <= F_out)."""

@@ -1,6 +1,6 @@
 """Packed records of a schedule's tail of rows of degree <= 2.
 
-The fused aggregate->transform launch (kgx_spmm_gemm_ex2) reads the rows of
+The fused aggregate->transform launch (kgx_work.tiny_pack) reads the rows of
 degree <= 2 at the end of the degree-descending schedule (on R-MAT about
 two thirds of all rows; the self loop alone is half) from one record each
 instead of an item plus index and weight loads: {row, degree, col0, col1}

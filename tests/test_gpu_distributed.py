@@ -454,7 +454,7 @@ def _run_wide_rank(rank, hub, dev, x128, x256, out):
         comm = ThreadComm(hub, rank)
         res = {}
         # GIN sum, 128 -> first Dense 128: the fused two-table pass with GIN's
-        # pre-scale (kgx_spmm_gemm_ex3, x2 + KGX_FUSED_PRE_GIN)
+        # pre-scale (kgx_spmm_gemm_run, x2 + KGX_FUSED_PRE_GIN)
         sg = kd.ShardedGraph.rmat(N, E, seed=10, device=dev, comm=comm, n_features=128, self_loops=False,
                                   gcn_norm=False, halo_chunks=2)
         gin = kd.ShardedGINConv(32, sg, mlp_hidden=[128], aggregator="sum", eps_init=0.5)
@@ -462,7 +462,7 @@ def _run_wide_rank(rank, hub, dev, x128, x256, out):
         with torch.no_grad():
             res["gin"] = (gin(xl).cpu().numpy(), gin.conv.get_weights())
         assert gin._fused(xl.contiguous())  # the MLP exists once built: the route the forward took
-        # GCN 256 -> 256: the weighted two-table 256-wide kernels (kgx_spmm_gemm_f256_ex)
+        # GCN 256 -> 256: the weighted two-table 256-wide kernels (kgx_spmm_gemm_f256_run with x2)
         sg2 = kd.ShardedGraph.rmat(N, E, seed=11, device=dev, comm=comm, n_features=256, halo_chunks=2)
         gcn = kd.ShardedGCNConv(256, sg2)
         xl2 = x256[sg2.lo: sg2.lo + sg2.n_local]

@@ -1,4 +1,4 @@
-"""kgx_spmm_gemm_f256 (fused aggregate -> transform for 256-wide rows, GINConv
+"""kgx_spmm_gemm_f256_run (fused aggregate -> transform for 256-wide rows, GINConv
 at BASELINE config C4) vs the oracle through the C-ABI (GPU).
 
 The aggregation half keeps the reference's sequential per-row order
@@ -234,7 +234,7 @@ def test_fused256_tiny_tail_bit_identical(dev, red, weighted, gin):
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("gin", [False, True])
 def test_fused256_two_tables_bit_identical(dev, weighted, gin):
-    """kgx_spmm_gemm_f256_ex with sources >= n_x1 read from a second table (the
+    """kgx_spmm_gemm_f256_run with sources >= n_x1 read from a second table (the
     sharded GIN layer's merged halo pass) equals the one-table launch over the
     concatenated table bit for bit -- main kernel, degree 3..7 launch, tiny tail
     and hub fix-up alike -- in the new-output, overwrite (accumulate=False, rows

@@ -1,5 +1,5 @@
 """The sliced schedule of the fused aggregate -> transform (kgx_slice_build,
-kgx_spmm_gemm_ex4): the builder's integer invariants, the sliced launch against
+kgx_fused_args.slice): the builder's integer invariants, the sliced launch against
 the float64 restatement (tests/fused_ref.py) and against the unsliced launch
 (rows below T bit-identical), its flags, non-finite inputs, and independence
 of the grid the main kernel is launched with.

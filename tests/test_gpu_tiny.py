@@ -1,5 +1,5 @@
 """The fused aggregate->transform's degree <= 2 tail on packed records
-(spmm_gemm_tiny_kernel, kgx_spmm_gemm_ex2) against the same launch with the
+(spmm_gemm_tiny_kernel, kgx_work.tiny_pack) against the same launch with the
 tail on the short-row kernel: same edges, same order, same split product, so
 the outputs must be bit-identical -- for every reduction, weighted and not,
 with the GIN pre-scale, ReLU, the accumulate form and the saved aggregate.

@@ -91,8 +91,8 @@ def test_host_array_key():
 
 def test_fused_shape_routing(monkeypatch):
     """Which shapes take a fused aggregate -> transform kernel: F_in 128 ->
-    128 (kgx_spmm_gemm), 256 -> 256 (kgx_spmm_gemm_f256; the sharded passes'
-    two-table gathers through kgx_spmm_gemm_f256_ex); KGX_FUSED256=0 /
+    128 (kgx_spmm_gemm), 256 -> 256 (kgx_spmm_gemm_f256_run; the sharded passes'
+    two-table gathers through its x2); KGX_FUSED256=0 /
     KGX_FUSED=0 turn them off."""
     from keras_geometric_amd import ops as kops
 
@@ -103,7 +103,7 @@ def test_fused_shape_routing(monkeypatch):
     assert not kops.fused_transform_supported(128, 256)  # F_in <= F_out but the 128 kernel stops at 128
     assert kops.fused_transform_supported(256, 256)
     assert not kops.fused_transform_supported(256, 128)  # transform first: narrower rows to gather
-    assert kops.fused_transform_supported(256, 256, two_table=True)  # sharded GIN at C4: kgx_spmm_gemm_f256_ex
+    assert kops.fused_transform_supported(256, 256, two_table=True)  # sharded GIN at C4: kgx_spmm_gemm_f256_run with x2
     assert kops.fused_transform_supported(128, 128, two_table=True)
     monkeypatch.setenv("KGX_FUSED256", "0")
     assert not kops.fused_transform_supported(256, 256) and kops.fused_transform_supported(128, 128)
@@ -144,7 +144,7 @@ def _cpu_graph(deg):
 
 
 def test_exact_short_start(monkeypatch):
-    """EXACT mode's short-row suffix (kgx_spmm_ex n_long_items with items = NULL):
+    """EXACT mode's short-row suffix (kgx_work.n_long_items with items = NULL):
     the index in the degree-descending row list where degree <= 7 starts; -1 when
     every row is short or none is, or with KGX_SHORT_ROWS=0."""
     monkeypatch.delenv("KGX_SHORT_ROWS", raising=False)

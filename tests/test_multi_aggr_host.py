@@ -1,7 +1,7 @@
 """Fused multi-aggregation, list aggregators and PNAConv without a device (CPU).
 
 * kgx_multi_aggr / kgx_multi_aggr_partials_floats are declared, exported and
-  bound; kgx_version() is still 1.
+  bound; kgx_version() is 2.
 * Every argument error is KGX_ERR_ARG before any device work: the CSR / table
   pointers are dummy addresses and `out` is a sentinel-filled host buffer that
   must come back untouched.
@@ -61,7 +61,7 @@ def test_declared_exported_bound_and_version(lib):
         assert re.search(rf"^int {name}\(", header, flags=re.M), name
         assert hasattr(lib, name), name
         assert name in _native.exported_symbols(), name
-    assert lib.kgx_version() == 1
+    assert lib.kgx_version() == 2
     assert "PNAConv" in kgx.__all__ and kgx.PNAConv is kgx.layers.PNAConv
     assert "MultiAggregator" in kgx.layers.__all__
     assert callable(kgx.ops.multi_aggregate)

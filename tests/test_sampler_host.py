@@ -56,7 +56,7 @@ def test_declared_exported_bound_and_public(lib):
         assert name in _native.exported_symbols(), name
     assert "NeighborSampler" in kgx.__all__ and "SampledSubgraph" in kgx.__all__
     assert kgx.NeighborSampler is kgx.sampling.NeighborSampler
-    assert lib.kgx_version() == 1
+    assert lib.kgx_version() == 2
 
 
 @pytest.mark.parametrize("kw, word", [

@@ -1,5 +1,5 @@
 """Host layout of the packed degree <= 2 tail (tiny.py) that the fused
-launch's tiny-row kernels read (include/kgx.h, kgx_spmm_gemm_ex2): built from
+launch's tiny-row kernels read (include/kgx.h, kgx_work.tiny_pack): built from
 a synthetic degree-descending schedule on the CPU and unpacked again."""
 
 from types import SimpleNamespace

@@ -8,7 +8,7 @@ offset of a 64-byte sector and spans 7 sectors (448 bytes), whichever lanes
 issue which 16-byte pieces; at a 448-byte stride (--ld 112) every row starts
 on a sector and spans exactly 7; at 512 (--ld 128) rows are whole 128-byte
 lines.  Same graph, same values in the first 100 columns, same kernel
-(kgx_spmm_ex2, MEAN), only the table's leading dimension changes: run each --ld
+(kgx_spmm_run, MEAN), only the table's leading dimension changes: run each --ld
 under rocprofv3 --pmc FETCH_SIZE to read the bytes fetched per launch, and
 without it for the time.  A measurement helper, not part of the product.
 
@@ -21,6 +21,7 @@ the last one, wherever it starts) and 128.  If the memory side moves whole
 """
 
 import argparse
+import ctypes
 import json
 import sys
 from pathlib import Path
@@ -56,15 +57,14 @@ def main():
     out = torch.empty(N, f, device=dev)
     items, _, split, _, n_slots = g.work(False)
     partials = torch.empty(max(n_slots, 1), f, device=dev)
-    n_items = items.shape[0]
-    n_split = 0 if split is None else split.shape[0]
+    a = nat.SpmmArgs(
+        struct_size=ctypes.sizeof(nat.SpmmArgs), reduce=nat.MEAN, epilogue=nat.EPI_NONE,
+        work=nat.work(g.rowptr, g.rows, items, split, g.col, None, g.n_long),
+        table=nat.addr(table), ld_table=table.stride(0), F=f, out=nat.addr(out), ld_out=out.stride(0), gin_scale=1.0,
+        partials=nat.addr(partials))
 
     def run():
-        nat.check(nat.lib().kgx_spmm_ex2(
-            nat.MEAN, nat.EPI_NONE, nat.ptr(g.rowptr), nat.ptr(g.rows), N, nat.ptr(items), n_items, g.n_long,
-            nat.ptr(split), n_split, nat.ptr(g.col), None, nat.ptr(table), table.stride(0), None, 0, f,
-            nat.ptr(out), out.stride(0), None, None, 0, 1.0, None, 0.0, 0, nat.ptr(partials), None,
-            nat.stream(dev)), "kgx_spmm_ex2")
+        nat.check(nat.lib().kgx_spmm_run(ctypes.byref(a), nat.stream(dev)), "kgx_spmm_run")
 
     for _ in range(2):
         run()

@@ -1,4 +1,4 @@
-"""The 256-wide fused kernel (kgx_spmm_gemm_f256) on the C4 graph, by part
+"""The 256-wide fused kernel (kgx_spmm_gemm_f256_run) on the C4 graph, by part
 (a measurement helper).
 
   python tools/exp_f256.py

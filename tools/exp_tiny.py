@@ -3,11 +3,12 @@
 
   python tools/exp_tiny.py
 
-Calls kgx_spmm_gemm_ex2 with and without the packed tail on the NS graph and
+Calls kgx_spmm_gemm_run with and without the packed tail on the NS graph and
 checks the two outputs agree (tolerance: both are f32-accurate transforms of
 the same in-order sums), then times both.
 """
 
+import ctypes
 import json
 import sys
 from pathlib import Path
@@ -50,12 +51,13 @@ def main(n=10_000_000, e=100_000_000, f=128, weighted=True, red=0):
     w = g.w if weighted else None
 
     def call(out, use_tiny):
-        nat.check(nat.lib().kgx_spmm_gemm_ex2(
-            red, nat.ptr(g.rowptr), nat.ptr(g.rows), n, nat.ptr(g.items), g.n_items, g.n_long,
-            start if use_tiny else g.n_items, nat.ptr(pack) if use_tiny else None,
-            nat.ptr(tw) if (use_tiny and weighted) else None, n2 if use_tiny else 0, nat.ptr(g.split), g.n_split,
-            nat.ptr(g.col), nat.ptr(w), nat.ptr(x), x.stride(0), f, nat.ptr(W), f, nat.ptr(b), 0, 1.0,
-            nat.ptr(out), out.stride(0), nat.ptr(partials), None, 0, nat.stream(dev)), "ex2")
+        work = nat.work(g.rowptr, g.rows, g.items, g.split, g.col, w, g.n_long, *(
+            (start, pack, tw if weighted else None, n2) if use_tiny else ()))
+        a = nat.FusedArgs(
+            struct_size=ctypes.sizeof(nat.FusedArgs), reduce=red, work=work, x=nat.addr(x), ld_x=x.stride(0), F_in=f,
+            W=nat.addr(W), F_out=f, bias=nat.addr(b), gin_scale=1.0, out=nat.addr(out), ld_out=out.stride(0),
+            partials=nat.addr(partials))
+        nat.check(nat.lib().kgx_spmm_gemm_run(ctypes.byref(a), nat.stream(dev)), "kgx_spmm_gemm_run")
 
     call(out_a, False)
     call(out_b, True)
