@@ -616,6 +616,67 @@ int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_row
                        const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * kgx_gatv2 with edge features (PyG's GATv2Conv with edge_dim, on the shared-
+ * weight layer): one projected edge row enters the score, and only the score.
+ * For the row's CSR slots t (source j_t = col[t], edge row eps_t):
+ *   z_t[c]  = (h_dst[i,h,c] + h_src[j_t,h,c]) + eps_t[h,c]
+ *                                     (two rounded fp32 adds, in this order)
+ *   s_t     = sum_c att[h,c] * leaky_relu(z_t[c], slope)
+ *   alpha_t = exp(s_t - m) / (sum_t' exp(s_t' - m) + 1e-10)
+ *   out[i,h,:] = sum_t alpha_t * mask_t * h_src[j_t,h,:]  (+ bias)
+ * The message stays h_src[j_t] (kgx_dot_attention_edge adds eps there too).
+ * e: the edge table [n_e, ld_e >= heads*channels], fp32, unit column stride.
+ * e_idx: the edge row of each CSR slot ([kept] int32); NULL: the slot itself
+ * (e is in CSR order).  A row outside [0, n_e) means the slot has no edge
+ * feature: its eps is zeros.  Nothing is read out of range.  e == NULL (or
+ * n_e == 0) is kgx_gatv2, which forwards here.  e joins the layout's alignment
+ * inputs (16-byte pointer and ld_e a multiple of 4 for the float4 layouts).
+ * Everything else -- schedule, partials, stats, dropout, bias -- is kgx_gatv2's.
+ * Errors, before any device work: as kgx_gatv2; with e given, KGX_ERR_ARG for
+ * ld_e < heads*channels, ld_e >= 2^31, and n_e outside [0, 2^31).
+ * ------------------------------------------------------------------------- */
+int kgx_gatv2_edge(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                   const int32_t* items, int64_t n_items,
+                   const int32_t* split, int64_t n_split,
+                   const int32_t* col, const float* h_src, const float* h_dst, int64_t ld_h,
+                   const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx,
+                   const float* att, int heads, int channels, float negative_slope,
+                   float* out, int64_t ld_out, const float* bias,
+                   float* partials, float* stats,
+                   const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Backward of kgx_gatv2_edge.  As kgx_gatv2_backward with z_t formed by the
+ * forward's two adds in both passes (so lrelu'(z_t) is taken at the forward's
+ * z_t), and one more gradient, written by the destination pass:
+ *   grad_e[eps_t][h,c] = ds_t * att[h,c] * lrelu'(z_t[c])      (lrelu'(0) = slope)
+ * grad_e: [n_e, ld_ge >= heads*channels].  The destination pass stores the row
+ * of every slot that has an edge row (chunks of a split row store their own
+ * slots' rows; no partials): one writer per element when no two slots share an
+ * edge row.  Rows of no kept slot are not written -- the caller zeroes them.
+ * t_e_idx: the edge row of each TRANSPOSED slot (required with e; the source
+ * pass gathers eps_t beside h_dst[i] and G_i).  e and grad_e join the layout's
+ * alignment inputs.  alpha_ws / ds_ws / partials as kgx_gatv2_backward.
+ * Errors, before any device work: as kgx_gatv2_backward; with e given,
+ * KGX_ERR_ARG for grad_e or t_e_idx missing, ld_e or ld_ge < heads*channels or
+ * >= 2^31, and n_e outside [0, 2^31).
+ * ------------------------------------------------------------------------- */
+int kgx_gatv2_edge_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_rows,
+                            const int32_t* items, int64_t n_items, const int32_t* split, int64_t n_split,
+                            const int32_t* col, const float* h_src, const float* h_dst, int64_t ld_h,
+                            const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx,
+                            const float* att, int heads, int channels, float negative_slope,
+                            const float* out, int64_t ld_out, const float* bias, const float* stats,
+                            const float* grad_out, int64_t ld_grad,
+                            const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+                            const int32_t* t_items, int64_t t_n_items, const int32_t* t_split, int64_t t_n_split,
+                            const int32_t* t_col, const int32_t* t_slot, const int32_t* t_e_idx,
+                            float* grad_h_src, float* grad_h_dst, int64_t ld_grad_h, float* grad_att,
+                            float* grad_e, int64_t ld_ge,
+                            float* alpha_ws, float* ds_ws, float* partials,
+                            const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Fused dot-product (query / key / value) graph attention: PyG's
  * TransformerConv message passing without edge features, in one pass with an
  * online segment softmax.  Destination row i, head h, edges e of the row

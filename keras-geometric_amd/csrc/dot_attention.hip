@@ -66,12 +66,6 @@ struct DotArgs {
   int64_t ld_ge;
 };
 
-// The edge row of slot t and whether it has one; the row to load from is clamped to 0 when it has none.
-__device__ __forceinline__ bool edge_row(const int32_t* idx, int32_t n_e, int32_t t, int32_t& r) {
-  r = idx ? idx[t] : t;
-  return uint32_t(r) < uint32_t(n_e);
-}
-
 // k' = k + eps, v' = v + eps (eps = 0 for a slot without an edge row): one rounded add each.
 template <int K>
 __device__ __forceinline__ void add_edge(float (&k)[K], float (&v)[K], const float (&e)[K], bool has) {

@@ -17,6 +17,13 @@
 // tolerance-checked (|a-b| <= 1e-5*max(1,|b|)), not bit-checked.  The softmax
 // numerator and denominator are accumulated in fp64 (exact to ~1e-7 even on
 // 10^5-edge hub rows; the fp64 FMAs are free in this HBM-bound kernel).
+//
+// With an edge table (kgx_gatv2_edge; PyG's GATv2Conv with edge_dim) a second
+// row is gathered per edge and enters the score only: z = (h_dst[i] + h_src[j])
+// + eps_e, two rounded adds in this order in the forward and both backward
+// kernels, so lrelu'(z) is taken at the forward's z.  The message stays
+// h_src[j].  The kernels are templated on that (kEdge), and the instantiations
+// without it are the code of the op without edge features.
 #include "kgx_attn.h"
 
 namespace kgx {
@@ -34,6 +41,12 @@ struct GatArgs {
   AttnOut o;  // stats keep the denominator l + 1e-10
   Drop drop;
   AttnLayout lay;
+  // edge features (kEdge kernels only): table [n_e, ld_e], the edge row of each slot (e_idx null: the
+  // slot itself); a row outside [0, n_e) is a slot without a feature
+  const float* e;
+  int64_t ld_e;
+  int32_t n_e;
+  const int32_t* e_idx;
 };
 
 // The reference's softmax: an epsilon-guarded denominator, plain exp weights
@@ -49,7 +62,7 @@ struct GatSoftmax {
   static __device__ __forceinline__ float weight(float s, float m) { return expf(s - m); }
 };
 
-template <int K>
+template <int K, bool kEdge>
 __global__ __launch_bounds__(kBlock) void gatv2_kernel(GatArgs a) {
   // edges per online-softmax block: 3 measured best at C3 (K = 4): 1.27 ms vs 1.41 at 8, 1.30 at 4
   constexpr int U = K <= 4 ? 3 : (K == 8 ? 3 : 2);
@@ -93,13 +106,29 @@ __global__ __launch_bounds__(kBlock) void gatv2_kernel(GatArgs a) {
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int k = 0; k < K; ++k) hs[u][k] = L.valid ? hs[u][k] : 0.0f;
+      // kEdge: the slot's edge row, loaded like hs; padding lanes and slots without a feature select 0
+      float ep[kEdge ? U : 1][K];
+      if constexpr (kEdge) {
+        bool he[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          he[u] = edge_row(a.e_idx, a.n_e, u < n ? e + u : end - 1, r);
+          vload<K>(ep[u], a.e + row_off(he[u] ? r : 0, a.ld_e) + L.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int k = 0; k < K; ++k) ep[u][k] = (L.valid && he[u]) ? ep[u][k] : 0.0f;
+      }
       float s[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float p = 0.0f;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-          const float g = hd[k] + hs[u][k];
+          float g = hd[k] + hs[u][k];
+          if constexpr (kEdge) g += ep[u][k];
           const float z = g > 0.0f ? g : g * a.slope;  // leaky_relu
           p += z * att[k];
         }
@@ -125,24 +154,30 @@ __global__ __launch_bounds__(kBlock) void gatv2_fixup_kernel(GatArgs a) {
 
 using namespace kgx;
 
-extern "C" int kgx_gatv2(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
-                         int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
-                         const float* h_src, const float* h_dst, int64_t ld_h, const float* att, int heads,
-                         int channels, float negative_slope, float* out, int64_t ld_out, const float* bias,
-                         float* partials, float* stats, const int32_t* drop_key, float drop_p,
-                         uint64_t drop_seed, kgx_stream_t stream_) {
+extern "C" int kgx_gatv2_edge(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
+                              int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
+                              const float* h_src, const float* h_dst, int64_t ld_h, const float* e, int64_t ld_e,
+                              int64_t n_e, const int32_t* e_idx, const float* att, int heads, int channels,
+                              float negative_slope, float* out, int64_t ld_out, const float* bias,
+                              float* partials, float* stats, const int32_t* drop_key, float drop_p,
+                              uint64_t drop_seed, kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
   KGX_REQUIRE(heads > 0 && channels > 0 && n_rows >= 0 && n_items >= 0 && n_split >= 0, KGX_ERR_ARG,
               "kgx_gatv2: bad sizes");
-  if (n_rows == 0) return KGX_OK;
   const int64_t HC = int64_t(heads) * channels;
+  const int64_t lim = int64_t(1) << 31;
+  KGX_REQUIRE(!e || (n_e >= 0 && n_e < lim), KGX_ERR_ARG, "kgx_gatv2: edge table rows outside [0, 2^31)");
+  KGX_REQUIRE(!e || ld_e >= HC, KGX_ERR_ARG, "kgx_gatv2: leading dimension of e < heads*channels");
+  KGX_REQUIRE(!e || ld_e < lim, KGX_ERR_ARG, "kgx_gatv2: leading dimension of e >= 2^31");
+  if (n_rows == 0) return KGX_OK;
+  if (e && n_e == 0) e = nullptr;  // no row to read: every slot is without a feature
   KGX_REQUIRE(rowptr && rows && col && h_src && h_dst && att && out, KGX_ERR_ARG, "kgx_gatv2: null pointer");
   KGX_REQUIRE(ld_h >= HC && ld_out >= HC, KGX_ERR_ARG, "kgx_gatv2: leading dimension < heads*channels");
   KGX_REQUIRE(ld_h < (int64_t(1) << 31), KGX_ERR_ARG, "kgx_gatv2: leading dimension >= 2^31");
   KGX_REQUIRE(!items || n_split == 0 || (split && partials), KGX_ERR_ARG,
               "kgx_gatv2: split rows need split list and partials");
   const auto fits = [&](int b) {
-    return attn_vec_ok(b, {h_src, h_dst, out, att, bias, partials}, {ld_h, ld_out});
+    return attn_vec_ok(b, {h_src, h_dst, out, att, bias, partials, e}, {ld_h, ld_out, e ? ld_e : 0});
   };
   const bool vec4 = fits(16);
   int K = attn_pick_k(heads, channels, vec4, fits(8));
@@ -165,10 +200,31 @@ extern "C" int kgx_gatv2(const int32_t* rowptr, const int32_t* rows, int64_t n_r
   a.o = {out, ld_out, partials, attn_partial_ld(heads, channels), stats, bias};
   a.drop = make_drop(drop_key, drop_p, drop_seed);
   a.lay = attn_layout(heads, channels, K);
+  if (!e) {
+    return dispatch_k(K, [&](auto k) {
+      constexpr int kK = decltype(k)::value;
+      return launch_with_fixup(gatv2_kernel<kK, false>, gatv2_fixup_kernel<kK>, a, stream);
+    });
+  }
+  a.e = e;
+  a.ld_e = ld_e;
+  a.n_e = int32_t(n_e);
+  a.e_idx = e_idx;
   return dispatch_k(K, [&](auto k) {
     constexpr int kK = decltype(k)::value;
-    return launch_with_fixup(gatv2_kernel<kK>, gatv2_fixup_kernel<kK>, a, stream);
+    return launch_with_fixup(gatv2_kernel<kK, true>, gatv2_fixup_kernel<kK>, a, stream);
   });
+}
+
+extern "C" int kgx_gatv2(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
+                         int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
+                         const float* h_src, const float* h_dst, int64_t ld_h, const float* att, int heads,
+                         int channels, float negative_slope, float* out, int64_t ld_out, const float* bias,
+                         float* partials, float* stats, const int32_t* drop_key, float drop_p,
+                         uint64_t drop_seed, kgx_stream_t stream_) {
+  return kgx_gatv2_edge(rowptr, rows, n_rows, items, n_items, split, n_split, col, h_src, h_dst, ld_h, nullptr, 0, 0,
+                        nullptr, att, heads, channels, negative_slope, out, ld_out, bias, partials, stats, drop_key,
+                        drop_p, drop_seed, stream_);
 }
 
 // ===========================================================================
@@ -189,6 +245,11 @@ extern "C" int kgx_gatv2(const int32_t* rowptr, const int32_t* rows, int64_t n_r
 // Kernel A stores alpha and ds per (edge, head); kernel B walks the
 // TRANSPOSED CSR (its own split schedule) and pulls d h_src -- no atomics
 // except the H*C-float d att.
+// kEdge (kgx_gatv2_edge_backward): z_e = (h_dst[i] + h_src[j_e]) + eps_e in
+// both kernels, by the forward's two adds, and kernel A, which has ds_e per
+// edge, stores d eps_e = dz_e into the edge's row of grad_e (chunks of a split
+// row store their own edges' rows: no partials); kernel B gathers eps_e beside
+// h_dst[i] and G_i.
 // ===========================================================================
 
 namespace kgx {
@@ -222,16 +283,26 @@ struct GatBwdArgs {
   float* grad_h_src;
   int64_t ld_gs;
   AttnLayout lay;
+  // edge features (kEdge kernels only), as GatArgs; t_e_idx: the edge row of each transposed slot
+  const float* e;
+  int64_t ld_e;
+  int32_t n_e;
+  const int32_t* e_idx;
+  const int32_t* t_e_idx;
+  float* grad_e;  // one row per kept slot's edge row, written by the destination pass
+  int64_t ld_ge;
 };
 
-template <int K>
+// Edges in flight per step.  kEdge gathers one more K-wide row per edge: at K = 16 the unroll is
+// halved so that no instantiation spills (DESIGN.md §13 has the registers).
+template <int K, bool kEdge>
 constexpr int bwd_unroll() {
-  return K <= 4 ? 8 : 4;
+  return K <= 4 ? 8 : ((kEdge && K == 16) ? 2 : 4);
 }
 
-template <int K>
+template <int K, bool kEdge>
 __global__ __launch_bounds__(kBlock) void gatv2_bwd_rows_kernel(GatBwdArgs a) {
-  constexpr int U = bwd_unroll<K>();
+  constexpr int U = bwd_unroll<K, kEdge>();
   const HeadLanes<K> L(a.lay, a.H, a.C);
   const int head = L.head, sub = L.sub, f = L.f;
   const bool valid = L.valid;
@@ -279,12 +350,34 @@ __global__ __launch_bounds__(kBlock) void gatv2_bwd_rows_kernel(GatBwdArgs a) {
         const int32_t ee = e + u < end ? e + u : end - 1;
         vload<K>(hs[u], a.h_src + row_off(a.col[ee], a.ld_h) + f);
       }
+      // kEdge: eps of each slot (0 without an edge row) and the row its gradient goes to (-1: none)
+      float ep[kEdge ? U : 1][K];
+      int32_t er[kEdge ? U : 1];
+      if constexpr (kEdge) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          const bool he = edge_row(a.e_idx, a.n_e, e + u < end ? e + u : end - 1, r);
+          vload<K>(ep[u], a.e + row_off(he ? r : 0, a.ld_e) + f);
+          er[u] = he ? r : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int k = 0; k < K; ++k) ep[u][k] = er[u] >= 0 ? ep[u][k] : 0.0f;
+      }
+      // z of the forward: (h_dst + h_src) + eps, the same two rounded adds
+      auto zin = [&](int u, int k) {
+        float g = hd[k] + hs[u][k];
+        if constexpr (kEdge) g += ep[u][k];
+        return g;
+      };
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float ps = 0.0f, pa = 0.0f;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-          ps += lrelu(hd[k] + hs[u][k]) * att[k];
+          ps += lrelu(zin(u, k)) * att[k];
           pa += gr[k] * hs[u][k];
         }
         const float sc = group_reduce(ps, a.lay.LH);
@@ -296,9 +389,17 @@ __global__ __launch_bounds__(kBlock) void gatv2_bwd_rows_kernel(GatBwdArgs a) {
           const float dsv = al * (dmu * da - D);
 #pragma unroll
           for (int k = 0; k < K; ++k) {
-            const float g = hd[k] + hs[u][k];
+            const float g = zin(u, k);
             gd[k] += dsv * att[k] * (g > 0.0f ? 1.0f : a.slope);
             gatt[k] += dsv * lrelu(g);
+          }
+          if constexpr (kEdge) {  // d eps = dz: the slot's edge row has its one writer here
+            if (valid && er[u] >= 0) {
+              float ge[K];
+#pragma unroll
+              for (int k = 0; k < K; ++k) ge[k] = dsv * att[k] * (zin(u, k) > 0.0f ? 1.0f : a.slope);
+              vstore<K>(a.grad_e + row_off(er[u], a.ld_ge) + f, ge);
+            }
           }
           if (valid && sub == 0) {
             a.alpha[int64_t(e + u) * a.H + head] = al * dmu;  // the message weight kernel B pulls with
@@ -317,9 +418,9 @@ __global__ __launch_bounds__(kBlock) void gatv2_bwd_rows_kernel(GatBwdArgs a) {
   }
 }
 
-template <int K>
+template <int K, bool kEdge>
 __global__ __launch_bounds__(kBlock) void gatv2_bwd_src_kernel(GatBwdArgs a) {
-  constexpr int U = bwd_unroll<K>();
+  constexpr int U = bwd_unroll<K, kEdge>();
   const HeadLanes<K> L(a.lay, a.H, a.C);
   const int head = L.head, f = L.f;
   const int HC = a.H * a.C;
@@ -347,12 +448,27 @@ __global__ __launch_bounds__(kBlock) void gatv2_bwd_src_kernel(GatBwdArgs a) {
         vload<K>(gr[u], a.grad + row_off(i, a.ld_g) + f);
         vload<K>(hd[u], a.h_dst + row_off(i, a.ld_h) + f);
       }
+      float ep[kEdge ? U : 1][K];  // kEdge: eps of each slot's edge, gathered beside h_dst[i] and G_i
+      if constexpr (kEdge) {
+        bool he[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int32_t r;
+          he[u] = edge_row(a.t_e_idx, a.n_e, e + u < end ? e + u : end - 1, r);
+          vload<K>(ep[u], a.e + row_off(he[u] ? r : 0, a.ld_e) + f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int k = 0; k < K; ++k) ep[u][k] = he[u] ? ep[u][k] : 0.0f;
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (e + u < end) {
 #pragma unroll
           for (int k = 0; k < K; ++k) {
-            const float g = hd[u][k] + hs[k];
+            float g = hd[u][k] + hs[k];
+            if constexpr (kEdge) g += ep[u][k];  // lrelu' at the forward's z
             acc[k] += al[u] * gr[u][k] + dsv[u] * att[k] * (g > 0.0f ? 1.0f : a.slope);
           }
         }
@@ -363,35 +479,43 @@ __global__ __launch_bounds__(kBlock) void gatv2_bwd_src_kernel(GatBwdArgs a) {
   }
 }
 
-template <int K>
+template <int K, bool kEdge>
 int launch_bwd(const GatBwdArgs& a, hipStream_t s) {
   const int HC = a.H * a.C;
-  if (const int rc = launch_resident(gatv2_bwd_rows_kernel<K>, a.sched.n_work(), a.lay.G, a, s)) return rc;
+  if (const int rc = launch_resident(gatv2_bwd_rows_kernel<K, kEdge>, a.sched.n_work(), a.lay.G, a, s)) return rc;
   if (const int rc = launch_chunk_sum(a.sched, a.partials, HC, HC, HC, a.grad_h_dst, a.ld_gd, a.grad_h_dst, a.ld_gd, s))
     return rc;
-  if (const int rc = launch_resident(gatv2_bwd_src_kernel<K>, a.t_sched.n_work(), a.lay.G, a, s)) return rc;
+  if (const int rc = launch_resident(gatv2_bwd_src_kernel<K, kEdge>, a.t_sched.n_work(), a.lay.G, a, s)) return rc;
   return launch_chunk_sum(a.t_sched, a.partials, HC, HC, HC, a.grad_h_src, a.ld_gs, a.grad_h_src, a.ld_gs, s);
 }
 
 }  // namespace
 }  // namespace kgx
 
-extern "C" int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
-                                  int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
-                                  const float* h_src, const float* h_dst, int64_t ld_h, const float* att, int heads,
-                                  int channels, float negative_slope, const float* out, int64_t ld_out,
-                                  const float* bias, const float* stats, const float* grad_out, int64_t ld_grad,
-                                  const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
-                                  const int32_t* t_items, int64_t t_n_items, const int32_t* t_split,
-                                  int64_t t_n_split, const int32_t* t_col, const int32_t* t_slot,
-                                  float* grad_h_src, float* grad_h_dst, int64_t ld_grad_h, float* grad_att,
-                                  float* alpha_ws, float* ds_ws, float* partials, const int32_t* drop_key,
-                                  float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
+extern "C" int kgx_gatv2_edge_backward(
+    const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items, int64_t n_items,
+    const int32_t* split, int64_t n_split, const int32_t* col, const float* h_src, const float* h_dst, int64_t ld_h,
+    const float* e, int64_t ld_e, int64_t n_e, const int32_t* e_idx, const float* att, int heads, int channels,
+    float negative_slope, const float* out, int64_t ld_out, const float* bias, const float* stats,
+    const float* grad_out, int64_t ld_grad, const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+    const int32_t* t_items, int64_t t_n_items, const int32_t* t_split, int64_t t_n_split, const int32_t* t_col,
+    const int32_t* t_slot, const int32_t* t_e_idx, float* grad_h_src, float* grad_h_dst, int64_t ld_grad_h,
+    float* grad_att, float* grad_e, int64_t ld_ge, float* alpha_ws, float* ds_ws, float* partials,
+    const int32_t* drop_key, float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
   KGX_REQUIRE(heads > 0 && channels > 0 && n_rows >= 0 && n_src >= 0 && n_items >= 0 && n_split >= 0 &&
                   t_n_items >= 0 && t_n_split >= 0,
               KGX_ERR_ARG, "kgx_gatv2_backward: bad sizes");
   const int64_t HC = int64_t(heads) * channels;
+  const int64_t lim = int64_t(1) << 31;
+  KGX_REQUIRE(!e || (n_e >= 0 && n_e < lim), KGX_ERR_ARG, "kgx_gatv2_backward: edge table rows outside [0, 2^31)");
+  KGX_REQUIRE(!e || (grad_e && t_e_idx), KGX_ERR_ARG, "kgx_gatv2_backward: an edge table needs grad_e and t_e_idx");
+  KGX_REQUIRE(!e || (ld_e >= HC && ld_ge >= HC), KGX_ERR_ARG,
+              "kgx_gatv2_backward: leading dimension of e or grad_e < heads*channels");
+  KGX_REQUIRE(!e || (ld_e < lim && ld_ge < lim), KGX_ERR_ARG,
+              "kgx_gatv2_backward: leading dimension of e or grad_e >= 2^31");
+  if (e && n_e == 0) e = nullptr;  // no row to read or write
+  if (!e) grad_e = nullptr;
   KGX_REQUIRE(rowptr && rows && col && h_src && h_dst && att && out && stats && grad_out && t_rowptr && t_rows &&
                   t_col && t_slot && grad_h_src && grad_h_dst && grad_att && alpha_ws && ds_ws,
               KGX_ERR_ARG, "kgx_gatv2_backward: null pointer");
@@ -402,8 +526,8 @@ extern "C" int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, in
   KGX_REQUIRE(((!items || n_split == 0) && (!t_items || t_n_split == 0)) || partials, KGX_ERR_ARG,
               "kgx_gatv2_backward: split rows need partials");
   const auto fits = [&](int b) {
-    return attn_vec_ok(b, {h_src, h_dst, att, grad_out, grad_h_src, grad_h_dst, out, bias, partials},
-                       {ld_h, ld_grad, ld_grad_h, ld_out});
+    return attn_vec_ok(b, {h_src, h_dst, att, grad_out, grad_h_src, grad_h_dst, out, bias, partials, e, grad_e},
+                       {ld_h, ld_grad, ld_grad_h, ld_out, e ? ld_e : 0, e ? ld_ge : 0});
   };
   const int K = attn_pick_k_smallest(heads, channels, fits(16), fits(8));
   KGX_REQUIRE(K > 0, KGX_ERR_UNSUPPORTED,
@@ -438,5 +562,31 @@ extern "C" int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, in
   a.grad_h_src = grad_h_src;
   a.ld_gs = ld_grad_h;
   a.lay = attn_layout(heads, channels, K);
-  return dispatch_k(K, [&](auto k) { return launch_bwd<decltype(k)::value>(a, stream); });
+  if (!e) return dispatch_k(K, [&](auto k) { return launch_bwd<decltype(k)::value, false>(a, stream); });
+  a.e = e;
+  a.ld_e = ld_e;
+  a.n_e = int32_t(n_e);
+  a.e_idx = e_idx;
+  a.t_e_idx = t_e_idx;
+  a.grad_e = grad_e;
+  a.ld_ge = ld_ge;
+  return dispatch_k(K, [&](auto k) { return launch_bwd<decltype(k)::value, true>(a, stream); });
+}
+
+extern "C" int kgx_gatv2_backward(const int32_t* rowptr, const int32_t* rows, int64_t n_rows, const int32_t* items,
+                                  int64_t n_items, const int32_t* split, int64_t n_split, const int32_t* col,
+                                  const float* h_src, const float* h_dst, int64_t ld_h, const float* att, int heads,
+                                  int channels, float negative_slope, const float* out, int64_t ld_out,
+                                  const float* bias, const float* stats, const float* grad_out, int64_t ld_grad,
+                                  const int32_t* t_rowptr, const int32_t* t_rows, int64_t n_src,
+                                  const int32_t* t_items, int64_t t_n_items, const int32_t* t_split,
+                                  int64_t t_n_split, const int32_t* t_col, const int32_t* t_slot,
+                                  float* grad_h_src, float* grad_h_dst, int64_t ld_grad_h, float* grad_att,
+                                  float* alpha_ws, float* ds_ws, float* partials, const int32_t* drop_key,
+                                  float drop_p, uint64_t drop_seed, kgx_stream_t stream_) {
+  return kgx_gatv2_edge_backward(rowptr, rows, n_rows, items, n_items, split, n_split, col, h_src, h_dst, ld_h,
+                                 nullptr, 0, 0, nullptr, att, heads, channels, negative_slope, out, ld_out, bias,
+                                 stats, grad_out, ld_grad, t_rowptr, t_rows, n_src, t_items, t_n_items, t_split,
+                                 t_n_split, t_col, t_slot, nullptr, grad_h_src, grad_h_dst, ld_grad_h, grad_att,
+                                 nullptr, 0, alpha_ws, ds_ws, partials, drop_key, drop_p, drop_seed, stream_);
 }

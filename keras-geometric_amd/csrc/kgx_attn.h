@@ -117,6 +117,13 @@ inline Drop make_drop(const int32_t* key, float p, uint64_t seed) {
 #define KGX_REQUIRE_DROP_P(p, fn) \
   KGX_REQUIRE((p) >= 0.0f && (p) < 1.0f, KGX_ERR_ARG, fn ": dropout p must be in [0, 1)")
 
+// Edge tables (kgx_dot_attention_edge, kgx_gatv2_edge): the edge row of slot t
+// (idx null: the slot itself) and whether it has one (a row inside [0, n_e)).
+__device__ __forceinline__ bool edge_row(const int32_t* idx, int32_t n_e, int32_t t, int32_t& r) {
+  r = idx ? idx[t] : t;
+  return uint32_t(r) < uint32_t(n_e);
+}
+
 // This thread's place in its row's lane group: K channels from `f` of `head`.
 // Padding lanes (head >= H, or a sub-lane past C) are not valid; their f is 0,
 // so they can load from a valid address and use nothing.

@@ -158,6 +158,19 @@ _SIGNATURES = {
         _i32p, _f32p, _f32p, _i64, _f32p, _int, _int, ctypes.c_float,
         _f32p, _i64, _f32p, _f32p, _f32p, _i32p, ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p,
     ],
+    "kgx_gatv2_edge": [
+        _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
+        _i32p, _f32p, _f32p, _i64, _f32p, _i64, _i64, _i32p, _f32p, _int, _int, ctypes.c_float,
+        _f32p, _i64, _f32p, _f32p, _f32p, _i32p, ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p,
+    ],
+    "kgx_gatv2_edge_backward": [
+        _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64, _i32p, _f32p, _f32p, _i64,
+        _f32p, _i64, _i64, _i32p, _f32p, _int, _int,
+        ctypes.c_float, _f32p, _i64, _f32p, _f32p, _f32p, _i64,
+        _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64, _i32p, _i32p, _i32p,
+        _f32p, _f32p, _i64, _f32p, _f32p, _i64, _f32p, _f32p, _f32p, _i32p, ctypes.c_float, ctypes.c_uint64,
+        ctypes.c_void_p,
+    ],
     "kgx_dot_attention": [
         _i32p, _i32p, _i64, _i32p, _i64, _i32p, _i64,
         _i32p, _f32p, _i64, _f32p, _i64, _f32p, _i64, _int, _int, ctypes.c_float,

@@ -6,7 +6,7 @@ torch.compile / symbolic tracing sees shapes without running the GPU.
 
   kgx::spmm   fused gather -> message -> segment {sum,mean,max,min,std} -> epilogue
   kgx::multi_aggr  several of those reducers from one gather, blocks concatenated
-  kgx::gatv2  fused GATv2 attention aggregation
+  kgx::gatv2  fused GATv2 attention aggregation (optionally with projected edge rows in the score)
   kgx::dot_attention  fused dot-product (query / key / value) attention aggregation
   kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
   kgx::edge_dot  edge scores from node rows (link prediction)
@@ -589,25 +589,41 @@ def _drop_args(drop_key, drop_p, drop_seed):
 
 
 def _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias,
-                n_slots, save_stats, drop_key=None, drop_p=0.0, drop_seed=0):
+                n_slots, save_stats, drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     h_src, h_dst, att, bias = _f32c(h_src), _f32c(h_dst), _f32c(att), _f32c(bias)
-    dev = nat.require_device(h_src, h_dst, rowptr, rows, col, att, bias, items, split)
-    n_dst = rowptr.numel() - 1
     HC = heads * channels
+    if edge is not None:
+        edge = _edge_table(edge, edge_idx, HC, col.numel(), "gatv2")
+    else:
+        edge_idx = None
+    dev = nat.require_device(h_src, h_dst, rowptr, rows, col, att, bias, items, split, edge, edge_idx)
+    n_dst = rowptr.numel() - 1
     out = torch.empty((n_dst, HC), dtype=torch.float32, device=dev)
     stats = torch.empty((n_dst if save_stats else 0, 2 * heads), dtype=torch.float32, device=dev)
     if n_dst == 0:
         return out, stats
     n_items, n_split = _sched_counts(items, split)
     partials = _attn_partials(dev, items, n_split, n_slots, heads, channels)
+    if edge is None:
+        nat.check(
+            nat.lib().kgx_gatv2(
+                nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split,
+                nat.ptr(col), nat.ptr(h_src), nat.ptr(h_dst), h_src.stride(0), nat.ptr(att), heads, channels,
+                float(negative_slope), nat.ptr(out), out.stride(0), nat.ptr(bias), nat.ptr(partials),
+                nat.ptr(stats) if save_stats else None, *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
+            ),
+            "kgx_gatv2",
+        )
+        return out, stats
     nat.check(
-        nat.lib().kgx_gatv2(
+        nat.lib().kgx_gatv2_edge(
             nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split,
-            nat.ptr(col), nat.ptr(h_src), nat.ptr(h_dst), h_src.stride(0), nat.ptr(att), heads, channels,
-            float(negative_slope), nat.ptr(out), out.stride(0), nat.ptr(bias), nat.ptr(partials),
-            nat.ptr(stats) if save_stats else None, *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
+            nat.ptr(col), nat.ptr(h_src), nat.ptr(h_dst), h_src.stride(0), nat.ptr(edge), _attn_ld(edge),
+            edge.shape[0], nat.ptr(edge_idx), nat.ptr(att), heads, channels, float(negative_slope), nat.ptr(out),
+            out.stride(0), nat.ptr(bias), nat.ptr(partials), nat.ptr(stats) if save_stats else None,
+            *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
         ),
-        "kgx_gatv2",
+        "kgx_gatv2_edge",
     )
     return out, stats
 
@@ -630,15 +646,17 @@ def gatv2_save(
     drop_key: Optional[torch.Tensor] = None,
     drop_p: float = 0.0,
     drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """kgx::gatv2 that also returns the per-row softmax statistics [n, 2*heads]."""
     return _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias,
-                       n_slots, True, drop_key, drop_p, drop_seed)
+                       n_slots, True, drop_key, drop_p, drop_seed, edge, edge_idx)
 
 
 @gatv2_save.register_fake
 def _gatv2_save_fake(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias,
-                     n_slots, drop_key=None, drop_p=0.0, drop_seed=0):
+                     n_slots, drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     n = rowptr.shape[0] - 1
     return h_src.new_empty((n, heads * channels)), h_src.new_empty((n, 2 * heads))
 
@@ -661,25 +679,29 @@ def gatv2(
     drop_key: Optional[torch.Tensor] = None,
     drop_p: float = 0.0,
     drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
+    """Fused GATv2 attention aggregation (kgx_gatv2); with `edge` [n_e, heads*channels], row
+    edge_idx[slot] (None: the slot) is added to h_dst[i] + h_src[j] in the score (kgx_gatv2_edge)."""
     return _gatv2_impl(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias,
-                       n_slots, False, drop_key, drop_p, drop_seed)[0]
+                       n_slots, False, drop_key, drop_p, drop_seed, edge, edge_idx)[0]
 
 
 @gatv2.register_fake
 def _gatv2_fake(h_src, h_dst, rowptr, rows, items, split, col, att, heads, channels, negative_slope, bias, n_slots,
-                drop_key=None, drop_p=0.0, drop_seed=0):
+                drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
     return h_src.new_empty((rowptr.shape[0] - 1, heads * channels))
 
 
-def _attn_table(t: torch.Tensor, width: int, what: str) -> torch.Tensor:
-    """A [n, heads*channels] fp32 table kgx_dot_attention reads in place: unit
-    column stride, non-overlapping rows (a column half of a wider tensor
+def _attn_table(t: torch.Tensor, width: int, what: str, op: str = "dot_attention") -> torch.Tensor:
+    """A [n, heads*channels] fp32 table the attention kernels read in place:
+    unit column stride, non-overlapping rows (a column half of a wider tensor
     passes through uncopied)."""
     if t.dtype != torch.float32:
         raise TypeError(f"kgx kernels compute in fp32; got {t.dtype}")
     if t.dim() != 2 or t.shape[1] != width:
-        raise ValueError(f"dot_attention: {what} must be [n, {width}], got {tuple(t.shape)}")
+        raise ValueError(f"{op}: {what} must be [n, {width}], got {tuple(t.shape)}")
     if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         return t.contiguous()
     return t
@@ -689,15 +711,116 @@ def _attn_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
-def _edge_table(edge, edge_idx, HC, n_slots_csr):
+def _edge_table(edge, edge_idx, HC, n_slots_csr, op: str = "dot_attention"):
     """The edge table as the kernels read it: [n_e, heads*channels] in place; without
     edge_idx its rows are the CSR slots."""
-    edge = _attn_table(edge, HC, "edge")
+    edge = _attn_table(edge, HC, "edge", op)
     if edge_idx is None and edge.shape[0] != n_slots_csr:
-        raise ValueError(f"dot_attention: edge in CSR order must have {n_slots_csr} rows, got {edge.shape[0]}")
+        raise ValueError(f"{op}: edge in CSR order must have {n_slots_csr} rows, got {edge.shape[0]}")
     if edge_idx is not None and (edge_idx.dtype != torch.int32 or edge_idx.numel() != n_slots_csr):
-        raise ValueError(f"dot_attention: edge_idx must be int32 [{n_slots_csr}]")
+        raise ValueError(f"{op}: edge_idx must be int32 [{n_slots_csr}]")
     return edge
+
+
+def gatv2_edge_backward_into(grad_e, grad_out, h_src, h_dst, att, bias, edge, out, stats, rowptr, rows, items, split,
+                             col, n_slots, t_rowptr, t_rows, t_items, t_split, t_col, t_slot, t_slots, heads,
+                             channels, negative_slope, edge_idx, t_edge_idx, drop_key=None, drop_p=0.0, drop_seed=0):
+    """(grad_h_src, grad_h_dst, grad_att) of kgx::gatv2_save with an edge table, and
+    d edge written into the rows of `grad_e` [n_e, heads*channels] (a row view of
+    a wider tensor is written in place) that a kept slot names: the caller
+    zeroes the others (kgx_gatv2_edge_backward)."""
+    HC = heads * channels
+    edge = _edge_table(edge, edge_idx, HC, col.numel(), "gatv2")
+    if t_edge_idx.dtype != torch.int32 or t_edge_idx.numel() != t_col.numel():
+        raise ValueError(f"gatv2: t_edge_idx must be int32 [{t_col.numel()}]")
+    if (grad_e.dtype != torch.float32 or grad_e.shape != edge.shape
+            or _attn_table(grad_e, HC, "grad_e", "gatv2") is not grad_e):
+        raise ValueError(f"gatv2: grad_e must be fp32 {tuple(edge.shape)} with unit column stride, got "
+                         f"{grad_e.dtype} {tuple(grad_e.shape)} strides {grad_e.stride()}")
+    grad_out, h_src, h_dst, out, stats = (_f32c(t) for t in (grad_out, h_src, h_dst, out, stats))
+    att, bias = _f32c(att.reshape(-1)), _f32c(bias)
+    dev = nat.require_device(grad_out, h_src, h_dst, att, bias, edge, grad_e, out, stats, rowptr, rows, items, split,
+                             col, t_rowptr, t_rows, t_items, t_split, t_col, t_slot, edge_idx, t_edge_idx, drop_key)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    g_src = torch.empty((n_src, HC), dtype=torch.float32, device=dev)
+    g_dst = torch.empty((n_dst, HC), dtype=torch.float32, device=dev)
+    g_att = torch.zeros(HC, dtype=torch.float32, device=dev)
+    if n_dst == 0 and n_src == 0:
+        return g_src, g_dst, g_att
+    kept = col.numel()
+    alpha = torch.empty((max(kept, 1), heads), dtype=torch.float32, device=dev)
+    ds = torch.empty_like(alpha)
+    partials = torch.empty((max(n_slots, t_slots, 1), HC), dtype=torch.float32, device=dev)
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
+    nat.check(
+        nat.lib().kgx_gatv2_edge_backward(
+            nat.ptr(rowptr), nat.ptr(rows), n_dst, nat.ptr(items), n_items, nat.ptr(split), n_split, nat.ptr(col),
+            nat.ptr(h_src), nat.ptr(h_dst), h_src.stride(0), nat.ptr(edge), _attn_ld(edge), edge.shape[0],
+            nat.ptr(edge_idx), nat.ptr(att), heads, channels, float(negative_slope), nat.ptr(out), out.stride(0),
+            nat.ptr(bias), nat.ptr(stats), nat.ptr(grad_out), grad_out.stride(0), nat.ptr(t_rowptr),
+            nat.ptr(t_rows), n_src, nat.ptr(t_items), t_n_items, nat.ptr(t_split), t_n_split, nat.ptr(t_col),
+            nat.ptr(t_slot), nat.ptr(t_edge_idx), nat.ptr(g_src), nat.ptr(g_dst), g_src.stride(0), nat.ptr(g_att),
+            nat.ptr(grad_e), _attn_ld(grad_e), nat.ptr(alpha), nat.ptr(ds), nat.ptr(partials),
+            *_drop_args(drop_key, drop_p, drop_seed), nat.stream(dev),
+        ),
+        "kgx_gatv2_edge_backward",
+    )
+    return g_src, g_dst, g_att
+
+
+@torch.library.custom_op("kgx::gatv2_edge_backward", mutates_args=())
+def gatv2_edge_backward(
+    grad_out: torch.Tensor,
+    h_src: torch.Tensor,
+    h_dst: torch.Tensor,
+    att: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    edge: torch.Tensor,
+    out: torch.Tensor,
+    stats: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_slot: torch.Tensor,
+    t_slots: int,
+    heads: int,
+    channels: int,
+    negative_slope: float,
+    edge_idx: Optional[torch.Tensor],
+    t_edge_idx: torch.Tensor,
+    zero_grad_edge: bool,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_h_src, grad_h_dst, grad_att [heads*channels], grad_edge) of kgx::gatv2_save with an
+    edge table; zero_grad_edge: some row of `edge` belongs to no kept slot."""
+    make = torch.zeros if zero_grad_edge or col.numel() == 0 else torch.empty
+    g_e = make((edge.shape[0], heads * channels), dtype=torch.float32, device=edge.device)
+    g_src, g_dst, g_att = gatv2_edge_backward_into(
+        g_e, grad_out, h_src, h_dst, att, bias, edge, out, stats, rowptr, rows, items, split, col, n_slots, t_rowptr,
+        t_rows, t_items, t_split, t_col, t_slot, t_slots, heads, channels, negative_slope, edge_idx, t_edge_idx,
+        drop_key, drop_p, drop_seed)
+    return g_src, g_dst, g_att, g_e
+
+
+@gatv2_edge_backward.register_fake
+def _gatv2_edge_backward_fake(grad_out, h_src, h_dst, att, bias, edge, out, stats, rowptr, rows, items, split, col,
+                              n_slots, t_rowptr, t_rows, t_items, t_split, t_col, t_slot, t_slots, heads, channels,
+                              negative_slope, edge_idx, t_edge_idx, zero_grad_edge, drop_key=None, drop_p=0.0,
+                              drop_seed=0):
+    hc = heads * channels
+    return (h_src.new_empty((t_rowptr.shape[0] - 1, hc)), h_src.new_empty((rowptr.shape[0] - 1, hc)),
+            h_src.new_empty((hc,)), h_src.new_empty((edge.shape[0], hc)))
 
 
 def _dot_attention_impl(q, k, v, rowptr, rows, items, split, col, heads, channels, scale, n_slots, save_stats,
@@ -1620,36 +1743,66 @@ def _fwd_slot32(t):
     return slot
 
 
-def _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, drop_p=0.0, drop_seed=0):
+def _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, drop_p=0.0, drop_seed=0,
+               edge=None, edge_order="input"):
     items, _, split, _, n_slots = g.work(exact)
     return _timed(lambda: torch.ops.kgx.gatv2(
         h_src, h_dst, g.rowptr, g.rows, items, split, g.col, att.reshape(-1), heads, channels,
         float(negative_slope), bias, n_slots, g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+        edge, g.eid if edge is not None and edge_order == "input" else None,
     ))
 
 
 class _GATv2Fn(torch.autograd.Function):
     """Autograd of the fused GATv2 aggregation: the forward keeps its output
     and per-row softmax statistics; kgx_gatv2_backward does one pass over the
-    destination CSR (d h_dst, d att, per-edge alpha / ds) and pulls d h_src
-    over the transposed CSR, both with hub rows split into chunks."""
+    destination CSR (d h_dst, d att, per-edge alpha / ds, and d edge with an
+    edge table) and pulls d h_src over the transposed CSR, both with hub rows
+    split into chunks."""
 
     @staticmethod
-    def forward(ctx, h_src, h_dst, att, bias, g, heads, channels, negative_slope, exact, drop_p, drop_seed):
+    def forward(ctx, h_src, h_dst, att, bias, g, heads, channels, negative_slope, exact, drop_p, drop_seed,
+                edge=None, edge_order="input"):
         ctx.g, ctx.heads, ctx.channels, ctx.slope, ctx.exact = g, heads, channels, float(negative_slope), exact
-        ctx.drop_p, ctx.drop_seed = drop_p, drop_seed
+        ctx.drop_p, ctx.drop_seed, ctx.edge_order = drop_p, drop_seed, edge_order
         items, _, split, _, n_slots = g.work(exact)
         out, stats = _timed(lambda: torch.ops.kgx.gatv2_save(
             h_src, h_dst, g.rowptr, g.rows, items, split, g.col, att.reshape(-1), heads, channels,
             float(negative_slope), bias, n_slots, g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+            edge, g.eid if edge is not None and edge_order == "input" else None,
         ))
-        ctx.save_for_backward(h_src, h_dst, att, bias, out, stats)
+        ctx.has_edge = edge is not None
+        ctx.save_for_backward(h_src, h_dst, att, bias, out, stats, *((edge,) if ctx.has_edge else ()))
         return out
+
+    @staticmethod
+    def _backward_edge(ctx, grad_out):
+        from . import graph as G
+
+        h_src, h_dst, att, bias, out, stats, edge = ctx.saved_tensors
+        g = ctx.g
+        t = G.transpose(g)
+        items, _, split, _, n_slots = g.work(ctx.exact)
+        t_items, _, t_split, _, t_slots = t.work(ctx.exact)
+        by_input = ctx.edge_order == "input"
+        # input order: the rows of input edges the graph dropped belong to no kept slot and stay zero
+        n_loops = g.n_dst if g.flags & nat.CSR_SELF_LOOPS else 0
+        unwritten = by_input and g.kept - n_loops != g.n_input_edges
+        g_src, g_dst, g_att, g_e = _timed(lambda: torch.ops.kgx.gatv2_edge_backward(
+            grad_out, h_src, h_dst, att.reshape(-1), bias, edge, out, stats, g.rowptr, g.rows, items, split, g.col,
+            n_slots, t.rowptr, t.rows, t_items, t_split, t.col, _fwd_slot32(t), t_slots, ctx.heads, ctx.channels,
+            ctx.slope, g.eid if by_input else None, t.eid if by_input else _fwd_slot32(t), unwritten,
+            g.eid if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed),
+        ))
+        g_bias = grad_out.sum(0) if ctx.needs_input_grad[3] else None
+        return (g_src, g_dst, g_att.view(att.shape), g_bias, None, None, None, None, None, None, None, g_e, None)
 
     @staticmethod
     def backward(ctx, grad_out):
         from . import graph as G
 
+        if ctx.has_edge:
+            return _GATv2Fn._backward_edge(ctx, grad_out)
         h_src, h_dst, att, bias, out, stats = ctx.saved_tensors
         g, H, C = ctx.g, ctx.heads, ctx.channels
         grad_out = grad_out.contiguous()
@@ -1681,7 +1834,7 @@ class _GATv2Fn(torch.autograd.Function):
             "kgx_gatv2_backward",
         )
         g_bias = grad_out.sum(0) if ctx.needs_input_grad[3] else None
-        return g_src, g_dst, g_att.view(att.shape), g_bias, None, None, None, None, None, None, None
+        return g_src, g_dst, g_att.view(att.shape), g_bias, None, None, None, None, None, None, None, None, None
 
 
 def gatv2_aggregate(
@@ -1696,13 +1849,35 @@ def gatv2_aggregate(
     exact: bool = False,
     dropout: float = 0.0,
     seed: int = 0,
+    edge: torch.Tensor | None = None,
+    edge_order: str = "input",
 ) -> torch.Tensor:
     """Fused GATv2 attention aggregation; differentiable in h_src, h_dst, att, bias.
-    dropout > 0: attention dropout of alpha per (edge, head), mask of (seed, input edge id, head)."""
-    if _needs_grad(h_src, h_dst, att, bias):
+    dropout > 0: attention dropout of alpha per (edge, head), mask of (seed, input edge id, head).
+
+    edge (PyG's edge_dim, already projected): one row per edge that is added to
+    h_dst[i] + h_src[j] in the score (not to the message); differentiable too, and a
+    column-slice view of a wider tensor is read in place.
+    edge_order="input": [g.n_input_edges, heads*channels] in input-edge order; the
+    self-loop slots a graph added carry no feature, unless the table has
+    g.n_input_edges + g.n_dst rows, whose rows E + i are then the loop of node i
+    (g.eid's loop id).  "csr": [g.kept, heads*channels] in CSR slot order, which
+    the kernel streams."""
+    if edge is not None:
+        if edge_order not in ("input", "csr"):
+            raise ValueError(f"gatv2: edge_order must be 'input' or 'csr', got {edge_order!r}")
+        hc = heads * channels
+        rows = [g.kept] if edge_order == "csr" else [g.n_input_edges]
+        if edge_order == "input" and g.flags & nat.CSR_SELF_LOOPS:
+            rows.append(g.n_input_edges + g.n_dst)
+        if edge.dim() != 2 or edge.shape[0] not in rows or edge.shape[1] != hc:
+            want = " or ".join(f"[{r}, {hc}]" for r in rows)
+            raise ValueError(f"gatv2: edge in {edge_order} order must be {want}, got {tuple(edge.shape)}")
+    if _needs_grad(h_src, h_dst, att, bias, edge):
         return _GATv2Fn.apply(h_src, h_dst, att, bias, g, heads, channels, negative_slope, exact, float(dropout),
-                              int(seed))
-    return _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, float(dropout), int(seed))
+                              int(seed), edge, edge_order)
+    return _gatv2_raw(g, h_src, h_dst, att, heads, channels, negative_slope, bias, exact, float(dropout), int(seed),
+                      edge, edge_order)
 
 
 def _dot_attention_raw(g, q, k, v, heads, channels, scale, exact, drop_p=0.0, drop_seed=0, edge=None,
