@@ -108,6 +108,10 @@ int kgx_cu_split_census(int per32, int64_t n_blocks, int32_t* head_ids, int32_t*
  *   rowptr[n_dst+1], col[cap] (source id per CSR slot), eid[cap] (input edge
  *   id per CSR slot; self loop i has id E+i), deg[n_dst] (int32 in-degree),
  *   optional dinv[n_dst] and w[cap] (KGX_CSR_GCN_NORM).
+ * KGX_ERR_ARG: SELF_LOOPS or GCN_NORM with n_src != n_dst (w indexes the one
+ *   dinv[n_dst] table with the source id; a bipartite graph takes
+ *   kgx_gcn_edge_norm with dinv_dst / dinv_src), and GCN_NORM together with
+ *   SEGMENT_ONLY (whose sources are neither range-checked nor wrapped).
  * info[4] (host) receives: kept edges, max in-degree, #bad indices, and
  * (kgx_csr_build2) the rows whose degree the dinv table did not cover.
  * This call synchronises `stream` once (to return info).
@@ -174,9 +178,12 @@ int kgx_gcn_edge_norm(const int32_t* rowptr, const int32_t* col, int64_t n_dst,
 
 /* ---------------------------------------------------------------------------
  * Row schedule (no reference counterpart: the reference has one device and no
- * scheduling).  Orders destination rows by descending degree (log2 buckets,
- * stable) so hub rows start first, and cuts rows with deg >= split_len into
- * split_len-edge chunks whose partials are combined in chunk order.
+ * scheduling).  Orders destination rows by descending exact degree (stable:
+ * ascending row id among equal degrees; degrees >= 2^24 - 1 tie) so hub rows
+ * start first, and cuts rows with deg >= split_len into split_len-edge chunks
+ * whose partials are combined in chunk order: chunk c of a row [beg, end) is
+ * [beg + c*split_len, min(end, beg + (c+1)*split_len)) with slot first_slot + c,
+ * and the slots of all split rows are dense in [0, n_slots).
  *   rows[n_dst]              row ids in schedule order (EXACT mode iterates these)
  *   items[4*cap_items]       {row, edge_begin, edge_end, partial_slot|-1}
  *   split[4*n_dst]           {row, first_slot, n_chunks, degree} for split rows

@@ -526,6 +526,14 @@ extern "C" int kgx_csr_build2(const int32_t* src, const int32_t* dst, int64_t E,
   KGX_REQUIRE(!loops || n_src == n_dst, KGX_ERR_ARG,
               "kgx_csr_build: self loops need n_src == n_dst (got %lld, %lld)", (long long)n_src,
               (long long)n_dst);
+  // w[e] = dinv[dst] * dinv[src] reads the one n_dst-entry table with the source id: the sources
+  // must be the same node set, and range-checked (SEGMENT_ONLY neither checks nor wraps them)
+  KGX_REQUIRE(!norm || n_src == n_dst, KGX_ERR_ARG,
+              "kgx_csr_build: GCN_NORM needs n_src == n_dst (got %lld, %lld); a bipartite graph takes "
+              "kgx_gcn_edge_norm with its two dinv tables",
+              (long long)n_src, (long long)n_dst);
+  KGX_REQUIRE(!norm || !(flags & KGX_CSR_SEGMENT_ONLY), KGX_ERR_ARG,
+              "kgx_csr_build: GCN_NORM cannot be combined with SEGMENT_ONLY (sources are not validated)");
   const int64_t total = E + (loops ? n_dst : 0);
   KGX_REQUIRE(total < (int64_t(1) << 31) - 1 && n_dst < (int64_t(1) << 31) - 1, KGX_ERR_ARG,
               "kgx_csr_build: graph too large for int32 CSR (E'=%lld)", (long long)total);

@@ -171,6 +171,11 @@ def build_csr(
     E = int(src.numel())
     if int(dst.numel()) != E:
         raise ValueError(f"src/dst length mismatch: {E} vs {dst.numel()}")
+    if gcn_norm and n_src != n_dst:  # w reads the one dinv[n_dst] table with the source id (kgx.h)
+        raise ValueError(f"build_csr: gcn_norm needs n_src == n_dst (got {n_src}, {n_dst}); a bipartite graph "
+                         "takes kgx_gcn_edge_norm with its two dinv tables")
+    if gcn_norm and segment_only:
+        raise ValueError("build_csr: gcn_norm cannot be combined with segment_only (sources are not validated)")
     flags = (
         (nat.CSR_SELF_LOOPS if self_loops else 0)
         | (nat.CSR_SEGMENT_ONLY if segment_only else 0)
