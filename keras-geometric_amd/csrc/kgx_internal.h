@@ -255,17 +255,26 @@ inline CuSplit* cu_split(int per32, hipStream_t caller) {
   }
   if (nh == 0 || nt == 0) return nullptr;
   CuSplit n;
-  const bool ok = hipExtStreamCreateWithCUMask(&n.head, 8, mh) == hipSuccess &&
-                  hipExtStreamCreateWithCUMask(&n.tail, 8, mt) == hipSuccess &&
-                  hipEventCreateWithFlags(&n.fork, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&n.jh, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&n.jt, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {  // release whatever was made: run unsplit
+  hipError_t e = hipExtStreamCreateWithCUMask(&n.head, 8, mh);
+  if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&n.tail, 8, mt);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&n.fork, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&n.jh, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&n.jt, hipEventDisableTiming);
+  if (e != hipSuccess) {  // release whatever was made: run unsplit
     if (n.head) (void)hipStreamDestroy(n.head);
     if (n.tail) (void)hipStreamDestroy(n.tail);
     if (n.fork) (void)hipEventDestroy(n.fork);
     if (n.jh) (void)hipEventDestroy(n.jh);
     if (n.jt) (void)hipEventDestroy(n.jt);
+    // A device may refuse a mask (a virtualised MI355X: "out of memory" for fewer than 8 of
+    // every 32 CUs on either stream).  The refusal is handled here, so it is taken off HIP's
+    // last-error slot: left there, the unsplit launch's KGX_CHECK_LAUNCH reports it as its own.
+    (void)hipGetLastError();
+    thread_local int noted = 0;  // one note per split refused, not one per launch
+    if (noted != per32)
+      std::fprintf(stderr, "kgx: no CU-masked streams for a %d-of-32 split (%s): fused launches run unsplit\n",
+                   per32, hipGetErrorString(e));
+    noted = per32;
     return nullptr;
   }
   n.device = dev;
