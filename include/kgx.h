@@ -1118,6 +1118,60 @@ int kgx_negative_edges(const int32_t* rowptr, const int32_t* col_sorted, int64_t
                        const int32_t* a, const int32_t* keys, int64_t P, int Q, uint64_t seed, int max_tries,
                        int flags, int32_t* out, int64_t ld_out, int32_t* stats, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * GINE: edge-feature messages summed per row, sum aggregation (edge_mp.hip; no
+ * reference counterpart, PyG's GINEConv).  For row i, its CSR slots t:
+ *   eps_t  = edge[e_t] W + bias     projected: D in [1, 32], edge [n_e, D], W [D, F], bias [F] or NULL
+ *   eps_t  = edge[e_t]              plain (D = 0, W NULL): edge [n_e, F]
+ *   out[i] = sum_t relu(x[col[t]] + eps_t)  (+ gin_scale * xroot[i] when xroot is given)
+ * e_t = eid[t], or t itself when eid is NULL (the table is in CSR slot order and
+ * n_e == n_slots).  Empty rows get the epilogue alone.  F a multiple of 4 in
+ * [4, 512] (else KGX_ERR_UNSUPPORTED before any device work); x, out, xroot, bias
+ * and a plain edge table are read four floats at a time (16-byte aligned, leading
+ * dimension a multiple of 4, else KGX_ERR_UNSUPPORTED).  The projection runs on
+ * bf16 MFMA with both operands split three ways (f32-accurate).  Nothing is
+ * summed with atomics: the same bits from run to run.
+ *   struct_size     sizeof of the struct, else KGX_ERR_ARG.
+ *   rowptr, col, row_of_slot   the CSR [n_rows + 1], [n_slots], and the row of
+ *       every slot [n_slots].
+ *   workspace       kgx_gine_workspace_bytes(n_slots, F, D, backward) bytes.
+ * kgx_gine_backward_run walks the TRANSPOSED CSR (t_rowptr [n_rows + 1] over
+ * source rows, t_col = the slot's destination, t_row_of_slot, t_eid = the
+ * slot's row of `edge`, required in both edge orders):
+ *   dz_t = gout[t_col[t]] * [z_t > 0],  grad_x[j] = sum of its slots' dz
+ *   plain:     grad_edge[t_eid[t]] = dz_t (rows no slot names are not written)
+ *   projected: grad_W [D, F] (contiguous) = sum_t edge_t^T dz_t, grad_bias [F] =
+ *              sum_t dz_t (required when bias is given), added in a fixed order.
+ * KGX_ERR_ARG with a message: a leading dimension below the width or >= 2^31,
+ * n_e / n_rows / n_slots outside [0, 2^31), a null operand, a missing gradient
+ * buffer, a workspace that is too small.  n_rows == 0: KGX_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_gine_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* col; const int32_t* row_of_slot; const int32_t* eid;
+  int64_t n_rows; int64_t n_slots;
+  const float* x; int64_t ld_x; int64_t F;
+  const float* edge; int64_t ld_edge; int64_t n_e; int64_t D;
+  const float* W; int64_t ld_w; const float* bias;
+  const float* xroot; int64_t ld_xroot; float gin_scale; float pad_;
+  float* out; int64_t ld_out;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_gine_args;
+typedef struct kgx_gine_backward_args {
+  uint64_t struct_size;
+  const int32_t* t_rowptr; const int32_t* t_col; const int32_t* t_row_of_slot; const int32_t* t_eid;
+  int64_t n_rows; int64_t n_slots;
+  const float* x; int64_t ld_x; int64_t F;
+  const float* edge; int64_t ld_edge; int64_t n_e; int64_t D;
+  const float* W; int64_t ld_w; const float* bias;
+  const float* gout; int64_t ld_gout;
+  float* grad_x; int64_t ld_gx; float* grad_edge; int64_t ld_ge; float* grad_W; float* grad_bias;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_gine_backward_args;
+int kgx_gine_workspace_bytes(int64_t n_slots, int64_t F, int64_t D, int backward, size_t* bytes);
+int kgx_gine_run(const kgx_gine_args* a, kgx_stream_t stream);
+int kgx_gine_backward_run(const kgx_gine_backward_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ from .layers import (
     GATv2Conv,
     GCNConv,
     GINConv,
+    GINEConv,
     GlobalPooling,
     MessagePassing,
     PNAConv,
@@ -39,6 +40,7 @@ __all__ = [
     "GATv2Conv",
     "GCNConv",
     "GINConv",
+    "GINEConv",
     "GlobalPooling",
     "GraphData",
     "MessagePassing",

@@ -78,6 +78,34 @@ class FusedArgs(ctypes.Structure):
     ]
 
 
+class GineArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("col", _i32p), ("row_of_slot", _i32p), ("eid", _i32p), ("n_rows", _i64), ("n_slots", _i64),
+        ("x", _f32p), ("ld_x", _i64), ("F", _i64),
+        ("edge", _f32p), ("ld_edge", _i64), ("n_e", _i64), ("D", _i64),
+        ("W", _f32p), ("ld_w", _i64), ("bias", _f32p),
+        ("xroot", _f32p), ("ld_xroot", _i64), ("gin_scale", _f32), ("pad_", _f32),
+        ("out", _f32p), ("ld_out", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+class GineBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("t_rowptr", _i32p), ("t_col", _i32p), ("t_row_of_slot", _i32p), ("t_eid", _i32p), ("n_rows", _i64),
+        ("n_slots", _i64),
+        ("x", _f32p), ("ld_x", _i64), ("F", _i64),
+        ("edge", _f32p), ("ld_edge", _i64), ("n_e", _i64), ("D", _i64),
+        ("W", _f32p), ("ld_w", _i64), ("bias", _f32p),
+        ("gout", _f32p), ("ld_gout", _i64),
+        ("grad_x", _f32p), ("ld_gx", _i64), ("grad_edge", _f32p), ("ld_ge", _i64), ("grad_W", _f32p),
+        ("grad_bias", _f32p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 # name -> argtypes (every entry point returns int unless listed in _RESTYPES)
 _SIGNATURES = {
     "kgx_version": [],
@@ -241,6 +269,9 @@ _SIGNATURES = {
         _f32p, _i64, _i64, _f32p, _i64, _i64, _i64, _i32p, _i32p, _i64, _i64,
         _i32p, _f32p, _i64, _i32p, ctypes.c_void_p,
     ],
+    "kgx_gine_workspace_bytes": [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_gine_run": [ctypes.POINTER(GineArgs), ctypes.c_void_p],
+    "kgx_gine_backward_run": [ctypes.POINTER(GineBackwardArgs), ctypes.c_void_p],
     "kgx_negative_edges": [
         _i32p, _i32p, _i64, _i64, _i32p, _i32p, _i64, _int, ctypes.c_uint64, _int, _int,
         _i32p, _i64, _i32p, ctypes.c_void_p,

@@ -17,6 +17,7 @@ from .decoders import DotProductDecoder
 from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
 from .gin_conv import GINConv
+from .gine_conv import GINEConv
 from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
@@ -33,6 +34,7 @@ __all__ = [
     "GATv2Conv",
     "GCNConv",
     "GINConv",
+    "GINEConv",
     "GlobalPooling",
     "Layer",
     "MaxAggregator",

@@ -2528,3 +2528,244 @@ def edge_dot_graph(g: CSRGraph, x_dst: torch.Tensor, x_src: torch.Tensor, *, che
     if check:
         _check_bad(bad, "edge_dot_graph")
     return out.reshape(-1)
+
+
+# ---------------------------------------------------------------------------
+# GINE: edge-feature messages, projected in the kernel (kgx_gine_run)
+# ---------------------------------------------------------------------------
+def _gine_table(t: torch.Tensor, width: int, what: str, vec: bool) -> torch.Tensor:
+    """A [n, width] fp32 table the GINE kernels read in place: unit column stride and
+    non-overlapping rows; vec: read four floats at a time, so 16-byte aligned rows
+    (anything else is copied)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"kgx kernels compute in fp32; got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"gine: {what} must be [n, {width}], got {tuple(t.shape)}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    if vec and (t.data_ptr() % 16 or (t.shape[0] > 1 and t.stride(0) % 4)):
+        return t.contiguous()
+    return t
+
+
+def gine_supported(F: int, D: int | None = None) -> bool:
+    """Shapes edge_mp.hip implements: F a multiple of 4 in [4, 512], D (projected variant) in [1, 32]."""
+    return F % 4 == 0 and 4 <= F <= 512 and (D is None or 1 <= D <= 32)
+
+
+def _gine_workspace(dev, n_slots: int, F: int, D: int, backward: bool) -> torch.Tensor:
+    n = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_gine_workspace_bytes(n_slots, F, D, int(backward), ctypes.byref(n)),
+              "kgx_gine_workspace_bytes")
+    return torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+
+
+def _gine_operands(x, edge, weight, bias):
+    F = x.shape[1]
+    D = 0 if weight is None else weight.shape[0]
+    x = _gine_table(x, F, "x", True)
+    edge = _gine_table(edge, D if D else F, "edge", D == 0)
+    if weight is not None:
+        weight = _gine_table(weight, F, "weight", False)
+    return x, edge, weight, _f32c(bias), F, D
+
+
+@torch.library.custom_op("kgx::gine", mutates_args=())
+def gine(
+    x: torch.Tensor,
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    row_of_slot: torch.Tensor,
+    edge: torch.Tensor,
+    edge_idx: Optional[torch.Tensor],
+    weight: Optional[torch.Tensor],
+    bias: Optional[torch.Tensor],
+    xroot: Optional[torch.Tensor],
+    gin_scale: float,
+) -> torch.Tensor:
+    """out[i] = sum_{t in row i} relu(x[col t] + eps_t) (+ gin_scale * xroot[i]); eps_t = edge[e_t] @ weight +
+    bias (weight [D <= 32, F]) or edge[e_t] (weight None); e_t = edge_idx[t], or t without edge_idx."""
+    x, edge, weight, bias, F, D = _gine_operands(x, edge, weight, bias)
+    if xroot is not None:
+        xroot = _gine_table(xroot, F, "xroot", True)
+    dev = nat.require_device(x, rowptr, col, row_of_slot, edge, edge_idx, weight, bias, xroot)
+    n_rows, n_slots = rowptr.numel() - 1, col.numel()
+    out = torch.empty((n_rows, F), dtype=torch.float32, device=dev)
+    ws = _gine_workspace(dev, n_slots, F, D, False)
+    a = nat.GineArgs(
+        struct_size=ctypes.sizeof(nat.GineArgs), rowptr=nat.addr(rowptr), col=nat.addr(col),
+        row_of_slot=nat.addr(row_of_slot), eid=nat.addr(edge_idx), n_rows=n_rows, n_slots=n_slots,
+        x=nat.addr(x), ld_x=_attn_ld(x), F=F, edge=nat.addr(edge), ld_edge=_attn_ld(edge), n_e=edge.shape[0], D=D,
+        W=nat.addr(weight), ld_w=_attn_ld(weight) if weight is not None else 0, bias=nat.addr(bias),
+        xroot=nat.addr(xroot), ld_xroot=_attn_ld(xroot) if xroot is not None else 0, gin_scale=float(gin_scale),
+        out=nat.addr(out), ld_out=F, workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_gine_run(ctypes.byref(a), nat.stream(dev)), "kgx_gine_run")
+    return out
+
+
+@gine.register_fake
+def _gine_fake(x, rowptr, col, row_of_slot, edge, edge_idx, weight, bias, xroot, gin_scale):
+    return x.new_empty((rowptr.shape[0] - 1, x.shape[1]))
+
+
+def gine_backward_into(grad_e, grad_out, x, edge, weight, bias, t_rowptr, t_col, t_row_of_slot, t_edge_idx):
+    """(grad_x, grad_weight, grad_bias) of kgx::gine over the transposed CSR.  Plain variant
+    (weight None): d edge is written into the rows of `grad_e` [n_e, F] that a slot names (a
+    column-slice view of a wider tensor is written in place; the caller zeroes the others) and
+    grad_weight / grad_bias are None."""
+    x, edge, weight, bias, F, D = _gine_operands(x, edge, weight, bias)
+    grad_out = _gine_table(grad_out, F, "grad_out", True)
+    if D == 0 and (grad_e is None or grad_e.dtype != torch.float32 or grad_e.shape != edge.shape
+                   or _gine_table(grad_e, F, "grad_e", True) is not grad_e):
+        raise ValueError(f"gine: grad_e must be fp32 {tuple(edge.shape)} with unit column stride and 16-byte "
+                         "aligned rows")
+    dev = nat.require_device(grad_out, x, edge, weight, bias, t_rowptr, t_col, t_row_of_slot, t_edge_idx, grad_e)
+    n_rows, n_slots = t_rowptr.numel() - 1, t_col.numel()
+    g_x = torch.empty((n_rows, F), dtype=torch.float32, device=dev)
+    g_w = torch.empty((D, F), dtype=torch.float32, device=dev) if D else None
+    g_b = torch.empty(F, dtype=torch.float32, device=dev) if D and bias is not None else None
+    ws = _gine_workspace(dev, n_slots, F, D, True)
+    a = nat.GineBackwardArgs(
+        struct_size=ctypes.sizeof(nat.GineBackwardArgs), t_rowptr=nat.addr(t_rowptr), t_col=nat.addr(t_col),
+        t_row_of_slot=nat.addr(t_row_of_slot), t_eid=nat.addr(t_edge_idx), n_rows=n_rows, n_slots=n_slots,
+        x=nat.addr(x), ld_x=_attn_ld(x), F=F, edge=nat.addr(edge), ld_edge=_attn_ld(edge), n_e=edge.shape[0], D=D,
+        W=nat.addr(weight), ld_w=_attn_ld(weight) if weight is not None else 0, bias=nat.addr(bias),
+        gout=nat.addr(grad_out), ld_gout=_attn_ld(grad_out), grad_x=nat.addr(g_x), ld_gx=F,
+        grad_edge=nat.addr(grad_e) if D == 0 else None, ld_ge=_attn_ld(grad_e) if D == 0 else 0,
+        grad_W=nat.addr(g_w), grad_bias=nat.addr(g_b), workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_gine_backward_run(ctypes.byref(a), nat.stream(dev)), "kgx_gine_backward_run")
+    return g_x, g_w, g_b
+
+
+@torch.library.custom_op("kgx::gine_backward", mutates_args=())
+def gine_backward(
+    grad_out: torch.Tensor,
+    x: torch.Tensor,
+    edge: torch.Tensor,
+    weight: Optional[torch.Tensor],
+    bias: Optional[torch.Tensor],
+    t_rowptr: torch.Tensor,
+    t_col: torch.Tensor,
+    t_row_of_slot: torch.Tensor,
+    t_edge_idx: torch.Tensor,
+    zero_grad_edge: bool,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_x, grad_edge, grad_weight, grad_bias) of kgx::gine; the ones the variant does not have are
+    empty.  zero_grad_edge: some row of `edge` belongs to no slot."""
+    F = x.shape[1]
+    none = x.new_empty(0)
+    if weight is None:
+        make = torch.zeros if zero_grad_edge or t_col.numel() == 0 else torch.empty
+        g_e = make((edge.shape[0], F), dtype=torch.float32, device=x.device)
+        g_x, _, _ = gine_backward_into(g_e, grad_out, x, edge, None, None, t_rowptr, t_col, t_row_of_slot, t_edge_idx)
+        return g_x, g_e, none, x.new_empty(0)
+    g_x, g_w, g_b = gine_backward_into(None, grad_out, x, edge, weight, bias, t_rowptr, t_col, t_row_of_slot,
+                                       t_edge_idx)
+    return g_x, none, g_w, g_b if g_b is not None else x.new_empty(0)
+
+
+@gine_backward.register_fake
+def _gine_backward_fake(grad_out, x, edge, weight, bias, t_rowptr, t_col, t_row_of_slot, t_edge_idx, zero_grad_edge):
+    F = x.shape[1]
+    g_x = x.new_empty((t_rowptr.shape[0] - 1, F))
+    if weight is None:
+        return g_x, x.new_empty((edge.shape[0], F)), x.new_empty(0), x.new_empty(0)
+    return g_x, x.new_empty(0), x.new_empty(tuple(weight.shape)), x.new_empty(F if bias is not None else 0)
+
+
+def _gine_raw(g, x, edge, weight, bias, edge_order, xroot, gin_scale):
+    from . import graph as G
+
+    return _timed(lambda: torch.ops.kgx.gine(x, g.rowptr, g.col, G.row_of_slot(g), edge,
+                                             g.eid if edge_order == "input" else None, weight, bias, xroot,
+                                             float(gin_scale)))
+
+
+class _GineFn(torch.autograd.Function):
+    """Autograd of the fused GINE aggregation: nothing but the inputs is kept; the backward is one
+    pass of the span kernel over the transposed CSR, which recomputes every slot's z."""
+
+    @staticmethod
+    def forward(ctx, x, edge, weight, bias, xroot, g, edge_order, gin_scale):
+        ctx.g, ctx.edge_order, ctx.gin_scale = g, edge_order, float(gin_scale)
+        ctx.save_for_backward(x, edge, weight, bias)
+        return _gine_raw(g, x, edge, weight, bias, edge_order, xroot, gin_scale)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        x, edge, weight, bias = ctx.saved_tensors
+        g = ctx.g
+        t = G.transpose(g)
+        by_input = ctx.edge_order == "input"
+        # input order: the rows of input edges the graph dropped belong to no slot and stay zero
+        unwritten = by_input and g.kept != g.n_input_edges
+        g_x, g_e, g_w, g_b = _timed(lambda: torch.ops.kgx.gine_backward(
+            grad_out, x, edge, weight, bias, t.rowptr, t.col, G.row_of_slot(t), t.eid if by_input else _fwd_slot32(t),
+            unwritten))
+        g_root = grad_out * ctx.gin_scale if ctx.needs_input_grad[4] else None
+        if weight is None:
+            return g_x, g_e, None, None, g_root, None, None, None
+        return g_x, None, g_w, g_b if bias is not None else None, g_root, None, None, None
+
+
+def _gine_composed(g, x, edge, weight, bias, edge_order, xroot, gin_scale):
+    """The composed form: [kept, F] messages in torch, reduced by edge id through kgx_spmm."""
+    eps = edge if weight is None else (edge @ weight + bias if bias is not None else edge @ weight)
+    if edge_order == "input":
+        eps = eps[g.eid.long()]
+    msg = torch.relu(x[g.col.long()] + eps)
+    table = msg.new_zeros((g.n_input_edges, x.shape[1])).index_copy(0, g.eid.long(), msg)
+    if xroot is None:
+        return aggregate(g, table, "sum", by_edge=True)
+    return aggregate(g, table, "sum", by_edge=True, epilogue=nat.EPI_GIN, xroot=xroot.contiguous(),
+                     gin_scale=gin_scale)
+
+
+def gine_aggregate(
+    g: CSRGraph,
+    x: torch.Tensor,
+    edge: torch.Tensor,
+    *,
+    weight: torch.Tensor | None = None,
+    bias: torch.Tensor | None = None,
+    edge_order: str = "input",
+    xroot: torch.Tensor | None = None,
+    gin_scale: float = 0.0,
+) -> torch.Tensor:
+    """GINE's aggregation, out[i] = sum_{j -> i} relu(x[j] + eps_ij) (+ gin_scale * xroot[i] with xroot),
+    in one fused pass (kgx_gine_run): no [E, F] message or projected edge tensor is written.
+
+    weight [D, F] (D <= 32), bias [F]: eps = edge @ weight + bias is formed inside the kernel from the raw
+    attributes edge [n_e, D]; differentiable in x, xroot, weight and bias (the attributes are inputs).
+    weight None: eps = edge [n_e, F], differentiable in edge too.  edge_order="input": rows in input-edge
+    order ([g.n_input_edges, .]); "csr": rows in CSR slot order ([g.kept, .]).  x and edge may be
+    column-slice views of wider tensors.  Shapes the kernel does not implement (gine_supported) take the
+    composed form through the by-edge ops.aggregate."""
+    if edge_order not in ("input", "csr"):
+        raise ValueError(f"gine: edge_order must be 'input' or 'csr', got {edge_order!r}")
+    if g.flags & nat.CSR_SELF_LOOPS:
+        raise ValueError("gine: the graph has added self-loop slots, which carry no edge feature; build it without")
+    if x.dim() != 2 or x.shape[0] != g.n_src:
+        raise ValueError(f"gine: x must be [{g.n_src}, F], got {tuple(x.shape)}")
+    F = x.shape[1]
+    if weight is None and bias is not None:
+        raise ValueError("gine: bias needs weight (the plain variant adds edge rows as they are)")
+    if weight is not None and (weight.dim() != 2 or weight.shape[1] != F):
+        raise ValueError(f"gine: weight must be [D, {F}], got {tuple(weight.shape)}")
+    rows, width = g.kept if edge_order == "csr" else g.n_input_edges, F if weight is None else weight.shape[0]
+    if edge.dim() != 2 or tuple(edge.shape) != (rows, width):
+        raise ValueError(f"gine: edge in {edge_order} order must be [{rows}, {width}], got {tuple(edge.shape)}")
+    if xroot is not None and tuple(xroot.shape) != (g.n_dst, F):
+        raise ValueError(f"gine: xroot must be [{g.n_dst}, {F}], got {tuple(xroot.shape)}")
+    if weight is not None and _needs_grad(edge):
+        raise NotImplementedError("gine: the projected variant has no gradient of edge (the attributes are inputs); "
+                                  "project outside and pass weight=None for one")
+    if not gine_supported(F, None if weight is None else width):
+        return _gine_composed(g, x, edge, weight, bias, edge_order, xroot, gin_scale)
+    if _needs_grad(x, edge, weight, bias, xroot):
+        return _GineFn.apply(x, edge, weight, bias, xroot, g, edge_order, float(gin_scale))
+    return _gine_raw(g, x, edge, weight, bias, edge_order, xroot, gin_scale)
