@@ -1172,6 +1172,46 @@ int kgx_gine_workspace_bytes(int64_t n_slots, int64_t F, int64_t D, int backward
 int kgx_gine_run(const kgx_gine_args* a, kgx_stream_t stream);
 int kgx_gine_backward_run(const kgx_gine_backward_args* a, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * R-GCN: per-relation aggregate and transform in one pass (rgcn.hip; no
+ * reference counterpart, PyG's RGCNConv with aggr "mean" or "sum").  The graph
+ * is the composite CSR over rows i * R + r (destination i, relation r):
+ *   S[i, r] = sum of x[col[t]] over the slots t of row i * R + r
+ *   out[i]  = bias + xroot[i] W_root + sum_r norm[i, r] S[i, r] W[r]
+ *   norm    = 1 / (slots of the row) with mean (an empty row adds 0), else 1
+ * W [R, F_in, F_out] and W_root [F_in, F_out] are contiguous; W_root and bias may
+ * be NULL (W_root given: xroot [n_rows, F_in] is required).  F_in a multiple of 4
+ * in [4, 128], F_out a multiple of 4 in [4, 256]; x, xroot, out and bias 16-byte
+ * aligned, leading dimensions multiples of 4 (else KGX_ERR_UNSUPPORTED, before
+ * any device work).  The products run on bf16 MFMA with both operands split
+ * three ways (f32-accurate).  No atomics: the same bits from run to run.
+ *   struct_size   sizeof of the struct, else KGX_ERR_ARG.
+ *   rowptr, col   the composite CSR: [n_rows * R + 1], [slots]; n_rows * R < 2^31.
+ *   pieces        int32 [n_pieces][3] = (node, slot_begin, slot_end): every node's
+ *       slots [rowptr[i R], rowptr[(i + 1) R]) as one piece, or cut into several
+ *       consecutive ones that follow each other in the list; the pieces of cut
+ *       nodes are the first n_split_pieces of the list.  Every node has a piece
+ *       (a node without slots an empty one), which is what writes its row.
+ *   workspace     kgx_rgcn_workspace_bytes(...) bytes, 16-byte aligned: the split
+ *       weight fragments and one partial row per piece of a cut node.
+ * KGX_ERR_ARG with a message: a leading dimension below the width or >= 2^31,
+ * a null operand, a workspace that is too small.  n_rows == 0: KGX_OK.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_rgcn_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* col; const int32_t* pieces;
+  int64_t n_pieces; int64_t n_split_pieces; int64_t n_rows; int64_t R;
+  const float* x; int64_t ld_x; int64_t F_in;
+  const float* W; const float* W_root; const float* bias; int64_t F_out;
+  const float* xroot; int64_t ld_xroot;
+  int32_t mean; int32_t pad_;
+  float* out; int64_t ld_out;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_rgcn_args;
+int kgx_rgcn_workspace_bytes(int64_t n_pieces, int64_t n_split_pieces, int64_t R, int64_t F_in, int64_t F_out,
+                             size_t* bytes);
+int kgx_rgcn_run(const kgx_rgcn_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .layers import (
     GlobalPooling,
     MessagePassing,
     PNAConv,
+    RGCNConv,
     SAGEConv,
     Set2Set,
     TransformerConv,
@@ -47,6 +48,7 @@ __all__ = [
     "NegativeSampler",
     "NeighborSampler",
     "PNAConv",
+    "RGCNConv",
     "SAGEConv",
     "SampledBlocks",
     "SampledSubgraph",

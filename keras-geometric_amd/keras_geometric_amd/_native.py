@@ -106,6 +106,20 @@ class GineBackwardArgs(ctypes.Structure):
     ]
 
 
+class RgcnArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("col", _i32p), ("pieces", _i32p),
+        ("n_pieces", _i64), ("n_split_pieces", _i64), ("n_rows", _i64), ("R", _i64),
+        ("x", _f32p), ("ld_x", _i64), ("F_in", _i64),
+        ("W", _f32p), ("W_root", _f32p), ("bias", _f32p), ("F_out", _i64),
+        ("xroot", _f32p), ("ld_xroot", _i64),
+        ("mean", ctypes.c_int32), ("pad_", ctypes.c_int32),
+        ("out", _f32p), ("ld_out", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 # name -> argtypes (every entry point returns int unless listed in _RESTYPES)
 _SIGNATURES = {
     "kgx_version": [],
@@ -272,6 +286,8 @@ _SIGNATURES = {
     "kgx_gine_workspace_bytes": [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_gine_run": [ctypes.POINTER(GineArgs), ctypes.c_void_p],
     "kgx_gine_backward_run": [ctypes.POINTER(GineBackwardArgs), ctypes.c_void_p],
+    "kgx_rgcn_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_rgcn_run": [ctypes.POINTER(RgcnArgs), ctypes.c_void_p],
     "kgx_negative_edges": [
         _i32p, _i32p, _i64, _i64, _i32p, _i32p, _i64, _int, ctypes.c_uint64, _int, _int,
         _i32p, _i64, _i32p, ctypes.c_void_p,

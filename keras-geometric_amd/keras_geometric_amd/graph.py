@@ -557,3 +557,72 @@ def clear_cache() -> None:
     from .layers import _edges
 
     _edges._HOST_CAST.clear()
+
+
+# ---------------------------------------------------------------------------
+# Typed edges: the composite (destination, relation) CSR of kgx_rgcn_run
+# ---------------------------------------------------------------------------
+# Slots of one piece of the R-GCN tile kernel.  One lane group walks a piece's slots one after the other
+# (four rows in flight), and a tile of 64 pieces is eight such walks per wave, so a tile of full pieces
+# costs 64 * piece_len gathered rows against about 640 for a tile of average nodes of a degree-10 graph.
+# 128 keeps the heaviest tiles (which start first) near a dozen average tiles, below a block slot's
+# share of a 1M-node launch (about 20 tiles at 3 blocks per CU), while an R-MAT's hub of 10^5 edges
+# leaves under 10^3 partial rows for the fix-up.  Derived from those counts, not measured.
+RGCN_PIECE_LEN = 128
+
+
+@dataclass
+class RelationGraph:
+    """build_relation_csr's result: `graph` has n_dst * num_relations rows, row i * R + r
+    listing the sources of the edges of type r into destination i (input order kept)."""
+
+    graph: CSRGraph
+    num_relations: int
+    n_src: int
+    n_dst: int
+    pieces: torch.Tensor  # int32 [n_pieces, 3]: node, slot_begin, slot_end (kgx.h, kgx_rgcn_args)
+    n_pieces: int
+    n_split_pieces: int  # the pieces of nodes cut into several: the first rows of `pieces`
+    piece_len: int
+
+
+def relation_pieces(rowptr: torch.Tensor, n_dst: int, R: int, piece_len: int) -> tuple[torch.Tensor, int]:
+    """(pieces, n_split_pieces) of a composite rowptr [n_dst * R + 1]: nodes by degree, descending
+    (stable), a node of more than piece_len slots cut every piece_len slots, its pieces in slot order."""
+    node_ptr = rowptr[:: R].long()  # [n_dst + 1]: the node's first slot
+    deg = node_ptr[1:] - node_ptr[:-1]
+    order = torch.sort(deg, descending=True, stable=True).indices
+    count = torch.clamp((deg[order] + piece_len - 1) // piece_len, min=1)
+    node = torch.repeat_interleave(order, count)
+    first = torch.cumsum(count, 0) - count  # a node's first piece
+    k = torch.arange(node.numel(), device=rowptr.device) - torch.repeat_interleave(first, count)
+    begin = node_ptr[node] + k * piece_len
+    end = torch.minimum(begin + piece_len, node_ptr[node + 1])
+    pieces = torch.stack([node, begin, end], 1).to(torch.int32).contiguous()
+    return pieces, int(count[count > 1].sum())
+
+
+def build_relation_csr(src: torch.Tensor, dst: torch.Tensor, edge_type: torch.Tensor, n_src: int, n_dst: int,
+                       num_relations: int, *, piece_len: int | None = None) -> RelationGraph:
+    """Typed COO (int32 device tensors) -> RelationGraph.  Edges with an endpoint out of range are
+    dropped as build_csr drops them; a type outside [0, num_relations) is an error."""
+    R = int(num_relations)
+    if R < 1:
+        raise ValueError(f"build_relation_csr: num_relations must be >= 1, got {num_relations}")
+    if n_src < n_dst:
+        raise ValueError(f"build_relation_csr: n_src = {n_src} < n_dst = {n_dst} (the root term reads x[:n_dst])")
+    if n_dst * R >= 2**31:
+        raise ValueError(f"build_relation_csr: n_dst * num_relations = {n_dst * R} does not fit int32 rows")
+    piece_len = RGCN_PIECE_LEN if piece_len is None else int(piece_len)
+    if piece_len < 1:
+        raise ValueError(f"build_relation_csr: piece_len must be positive, got {piece_len}")
+    if edge_type.dtype != torch.int32 or edge_type.shape != dst.shape:
+        raise TypeError("build_relation_csr expects int32 edge_type, one per edge")
+    if edge_type.numel() and bool(((edge_type < 0) | (edge_type >= R)).any()):
+        raise ValueError(f"build_relation_csr: an edge type outside [0, {R})")
+    ok = (dst >= 0) & (dst < n_dst)
+    key = torch.where(ok, dst * R + edge_type, torch.full_like(dst, -1))
+    g = build_csr(src, key, n_src, n_dst * R)
+    pieces, n_split = relation_pieces(g.rowptr, n_dst, R, piece_len)
+    return RelationGraph(graph=g, num_relations=R, n_src=n_src, n_dst=n_dst, pieces=pieces,
+                         n_pieces=int(pieces.shape[0]), n_split_pieces=n_split, piece_len=piece_len)

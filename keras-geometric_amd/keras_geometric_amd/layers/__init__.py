@@ -21,6 +21,7 @@ from .gine_conv import GINEConv
 from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
+from .rgcn_conv import RGCNConv
 from .sage_conv import SAGEConv
 from .transformer_conv import TransformerConv
 
@@ -43,6 +44,7 @@ __all__ = [
     "MinAggregator",
     "MultiAggregator",
     "PNAConv",
+    "RGCNConv",
     "PoolingAggregator",
     "SAGEConv",
     "Sequential",

@@ -2769,3 +2769,118 @@ def gine_aggregate(
     if _needs_grad(x, edge, weight, bias, xroot):
         return _GineFn.apply(x, edge, weight, bias, xroot, g, edge_order, float(gin_scale))
     return _gine_raw(g, x, edge, weight, bias, edge_order, xroot, gin_scale)
+
+
+# ---------------------------------------------------------------------------
+# R-GCN: per-relation aggregate and transform (kgx_rgcn_run)
+# ---------------------------------------------------------------------------
+def rgcn_supported(F_in: int, F_out: int) -> bool:
+    """Shapes rgcn.hip implements: multiples of 4, F_in in [4, 128], F_out in [4, 256]."""
+    return F_in % 4 == 0 and 4 <= F_in <= 128 and F_out % 4 == 0 and 4 <= F_out <= 256
+
+
+def rgcn_into(out: torch.Tensor, rg, x: torch.Tensor, weight: torch.Tensor, root: torch.Tensor | None = None,
+              bias: torch.Tensor | None = None, *, mean: bool = True) -> torch.Tensor:
+    """The fused kernel writing `out` [n_dst, F_out] in place; x and out may be column-slice views of
+    wider tensors (unit column stride, 16-byte aligned rows).  No autograd."""
+    g, R = rg.graph, rg.num_relations
+    F_in, F_out = weight.shape[1], weight.shape[2]
+    x = _gine_table(x, F_in, "x", True)
+    if tuple(out.shape) != (rg.n_dst, F_out) or out.dtype != torch.float32 or _gine_table(out, F_out, "out", True) is not out:
+        raise ValueError(f"rgcn: out must be fp32 [{rg.n_dst}, {F_out}] with unit column stride and 16-byte aligned rows")
+    weight, root, bias = _f32c(weight), _f32c(root), _f32c(bias)
+    dev = nat.require_device(x, out, weight, root, bias, g.rowptr, g.col, rg.pieces)
+    n = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_rgcn_workspace_bytes(rg.n_pieces, rg.n_split_pieces, R, F_in, F_out, ctypes.byref(n)),
+              "kgx_rgcn_workspace_bytes")
+    ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+    a = nat.RgcnArgs(
+        struct_size=ctypes.sizeof(nat.RgcnArgs), rowptr=nat.addr(g.rowptr), col=nat.addr(g.col),
+        pieces=nat.addr(rg.pieces), n_pieces=rg.n_pieces, n_split_pieces=rg.n_split_pieces, n_rows=rg.n_dst, R=R,
+        x=nat.addr(x), ld_x=_attn_ld(x), F_in=F_in, W=nat.addr(weight), W_root=nat.addr(root), bias=nat.addr(bias),
+        F_out=F_out, xroot=nat.addr(x), ld_xroot=_attn_ld(x), mean=int(mean), out=nat.addr(out),
+        ld_out=_attn_ld(out), workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_rgcn_run(ctypes.byref(a), nat.stream(dev)), "kgx_rgcn_run")
+    return out
+
+
+def _rgcn_check(rg, x, weight, root, bias, aggr):
+    if aggr not in ("mean", "sum"):
+        raise ValueError(f"rgcn: aggr must be 'mean' or 'sum', got {aggr!r}")
+    if x.dim() != 2 or x.shape[0] != rg.n_src:
+        raise ValueError(f"rgcn: x must be [{rg.n_src}, F_in], got {tuple(x.shape)}")
+    F_in = x.shape[1]
+    if weight.dim() != 3 or tuple(weight.shape[:2]) != (rg.num_relations, F_in):
+        raise ValueError(f"rgcn: weight must be [{rg.num_relations}, {F_in}, F_out], got {tuple(weight.shape)}")
+    F_out = weight.shape[2]
+    if root is not None and tuple(root.shape) != (F_in, F_out):
+        raise ValueError(f"rgcn: root must be [{F_in}, {F_out}], got {tuple(root.shape)}")
+    if bias is not None and tuple(bias.shape) != (F_out,):
+        raise ValueError(f"rgcn: bias must be [{F_out}], got {tuple(bias.shape)}")
+    return F_in, F_out
+
+
+def _rgcn_composed(rg, x, weight, root, bias, aggr):
+    """The composed form: the [n_dst * R, F_in] table of per-pair aggregates (kgx_spmm over the
+    composite graph), then one dense map against the stacked weights, the root map and the bias."""
+    R, F_in, F_out = weight.shape
+    H = aggregate(rg.graph, x.contiguous(), aggr)
+    return dense(H.view(rg.n_dst, R * F_in), weight.reshape(R * F_in, F_out), bias,
+                 x1=None if root is None else x[: rg.n_dst], W1=root)
+
+
+class _RgcnFn(torch.autograd.Function):
+    """Fused forward; the backward is composed from kgx_spmm, kgx_gemm_tn and the library GEMM: H is
+    recomputed, nothing but the inputs is kept."""
+
+    @staticmethod
+    def forward(ctx, x, weight, root, bias, rg, mean):
+        ctx.rg, ctx.mean = rg, mean
+        ctx.save_for_backward(x, weight, root, bias)
+        out = torch.empty((rg.n_dst, weight.shape[2]), dtype=torch.float32, device=x.device)
+        return _timed(lambda: rgcn_into(out, rg, x, weight, root, bias, mean=mean))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, root, bias = ctx.saved_tensors
+        rg, g = ctx.rg, ctx.rg.graph
+        R, F_in, F_out = weight.shape
+        red = nat.MEAN if ctx.mean else nat.SUM
+        gout = grad_out.contiguous()
+        xroot = x[: rg.n_dst]
+        g_x = g_w = g_root = g_b = None
+        if ctx.needs_input_grad[1]:
+            H = _aggregate_raw(g, x.contiguous(), red, False, False, nat.EPI_NONE, None, None, 1.0, False)
+            g_w = gemm_tn(H.view(rg.n_dst, R * F_in), gout)[0].view(R, F_in, F_out)
+        want_b = bias is not None and ctx.needs_input_grad[3]
+        if root is not None and ctx.needs_input_grad[2]:
+            g_root, g_b = gemm_tn(xroot, gout, with_db=want_b)
+        elif want_b:
+            g_b = gout.sum(0)
+        if ctx.needs_input_grad[0]:
+            Z = _matmul_t(gout, weight.reshape(R * F_in, F_out)).view(rg.n_dst * R, F_in)
+            g_x = _reduce_backward(g, red, False, False, None, Z, False, rg.n_src)  # slot weight: the pair's norm
+            if root is not None:
+                g_x[: rg.n_dst] += _matmul_t(gout, root)
+        return g_x, g_w, g_root, g_b, None, None
+
+
+def rgcn_aggregate(rg, x: torch.Tensor, weight: torch.Tensor, root: torch.Tensor | None = None,
+                   bias: torch.Tensor | None = None, *, aggr: str = "mean", fused: bool | None = None) -> torch.Tensor:
+    """R-GCN's layer map (PyG's RGCNConv): out[i] = bias + x[i] @ root + sum_r norm[i, r] * (sum of x[j] over
+    the edges j -> i of type r) @ weight[r], norm = 1 / (that edge count) for "mean", 1 for "sum".
+
+    rg: graph.build_relation_csr's result; weight [R, F_in, F_out], root [F_in, F_out], bias [F_out].
+    fused=None takes the one-pass kernel (kgx_rgcn_run: the [n_dst, R * F_in] table of per-relation
+    aggregates is never written) on the shapes it implements (rgcn_supported) and the composed form
+    (kgx_spmm over the composite graph, then kgx_dense) elsewhere; fused=False is the composed form.
+    Differentiable in x, weight, root and bias; the fused op's backward is composed from kgx_spmm and
+    kgx_gemm_tn and is deterministic."""
+    F_in, F_out = _rgcn_check(rg, x, weight, root, bias, aggr)
+    if fused is False or not rgcn_supported(F_in, F_out):
+        return _rgcn_composed(rg, x, weight, root, bias, aggr)
+    if _needs_grad(x, weight, root, bias):
+        return _RgcnFn.apply(x, weight, root, bias, rg, aggr == "mean")
+    out = torch.empty((rg.n_dst, F_out), dtype=torch.float32, device=x.device)
+    return _timed(lambda: rgcn_into(out, rg, x, weight, root, bias, mean=aggr == "mean"))
