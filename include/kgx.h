@@ -1212,6 +1212,71 @@ int kgx_rgcn_workspace_bytes(int64_t n_pieces, int64_t n_split_pieces, int64_t R
                              size_t* bytes);
 int kgx_rgcn_run(const kgx_rgcn_args* a, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * GAT: scalar-score graph attention (gat.hip; no reference counterpart, PyG's
+ * GATConv).  The score is a sum of per-node and per-edge scalars per head:
+ *   z_e = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h]      s_e = leaky_relu(z_e)
+ *   alpha_e = exp(s_e - max) / (sum + 1e-16) over the in-edges of i
+ *   out[i,h,:] = sum_e alpha_e * drop_e * h_src[j_e,h,:]  (+ bias)
+ * z is formed by these two rounded fp32 adds, in this order, in every kernel.
+ * The schedule (rowptr .. n_split), col, out, bias, partials, stats and the
+ * dropout key are those of kgx_gatv2.  h_src [n_src, ld_h]; a_src [n_src, ld_as],
+ * a_dst [n_rows, ld_ad] and a_edge [n_e, ld_ae] hold `heads` floats per row and
+ * may be column views of wider tables (no alignment is asked of them).  a_edge
+ * NULL: no edge term; else the edge row of CSR slot t is e_idx[t] (e_idx NULL:
+ * t itself), and a row outside [0, n_e) counts as 0.  A row without edges stores
+ * the bias.  Every (heads, channels) that fits 64 lanes per row, else
+ * KGX_ERR_UNSUPPORTED; struct_size must be sizeof of the struct (KGX_ERR_ARG).
+ *
+ * kgx_gat_backward, with G = grad_out, D[i,h] = <G[i,h,:], out[i,h,:] - bias> and
+ * stats [n_rows, 2 * heads] = (max, denominator) from the forward:
+ *   p_e  = exp(s_e - m_i) / den_i      ds_e = p_e (drop_e <G_i, h_j>_h - D[i,h])
+ *   dz_e = ds_e * leaky_relu'(z_e)     (leaky_relu'(0) = negative_slope)
+ *   grad_h_src[j]   = sum_{e: j_e = j} p_e drop_e G_i
+ *   grad_a_src[j,h] = sum_{e: j_e = j} dz_e      grad_a_dst[i,h] = sum_{e into i} dz_e
+ *   grad_a_edge[e,h] = dz_e   (rows no slot names are not written)
+ * It walks the TRANSPOSED CSR (t_rowptr [n_src + 1] with its own schedule,
+ * t_col = the slot's destination, t_slot = its forward CSR slot, t_key = its
+ * dropout key, t_e_idx = its edge row, required with a_edge) with one row gather
+ * per edge, then sums each destination's dz over the forward schedule.  n_kept:
+ * the CSR's slots; n_slots / t_n_slots: the chunk slots of the two schedules.
+ * workspace: kgx_gat_backward_workspace_bytes(...) bytes, 16-byte aligned.  No
+ * atomics: out and every gradient are the same bits from run to run.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_gat_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split;
+  const int32_t* col;
+  const float* h_src; int64_t ld_h;
+  const float* a_src; int64_t ld_as; const float* a_dst; int64_t ld_ad;
+  const float* a_edge; int64_t ld_ae; int64_t n_e; const int32_t* e_idx;
+  int32_t heads; int32_t channels; float negative_slope; float drop_p;
+  const float* bias; float* out; int64_t ld_out; float* partials; float* stats;
+  const int32_t* drop_key; uint64_t drop_seed;
+} kgx_gat_args;
+typedef struct kgx_gat_backward_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split; int64_t n_slots;
+  const int32_t* t_rowptr; const int32_t* t_rows; int64_t n_src;
+  const int32_t* t_items; int64_t t_n_items; const int32_t* t_split; int64_t t_n_split; int64_t t_n_slots;
+  const int32_t* t_col; const int32_t* t_slot; const int32_t* t_key; const int32_t* t_e_idx; int64_t n_kept;
+  const float* h_src; int64_t ld_h;
+  const float* a_src; int64_t ld_as; const float* a_dst; int64_t ld_ad;
+  const float* a_edge; int64_t ld_ae; int64_t n_e;
+  int32_t heads; int32_t channels; float negative_slope; float drop_p; uint64_t drop_seed;
+  const float* out; int64_t ld_out; const float* bias; const float* stats;
+  const float* grad_out; int64_t ld_grad;
+  float* grad_h_src; int64_t ld_gh; float* grad_a_src; int64_t ld_gas;
+  float* grad_a_dst; int64_t ld_gad; float* grad_a_edge; int64_t ld_gae;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_gat_backward_args;
+int kgx_gat(const kgx_gat_args* a, kgx_stream_t stream);
+int kgx_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_kept, int64_t n_slots, int64_t t_n_slots, int heads,
+                                     int channels, size_t* bytes);
+int kgx_gat_backward(const kgx_gat_backward_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .layers import (
     AttentionPooling,
     BatchGlobalPooling,
     DotProductDecoder,
+    GATConv,
     GATv2Conv,
     GCNConv,
     GINConv,
@@ -38,6 +39,7 @@ __all__ = [
     "CSRGraph",
     "DotProductDecoder",
     "EdgeBatch",
+    "GATConv",
     "GATv2Conv",
     "GCNConv",
     "GINConv",

@@ -120,6 +120,42 @@ class RgcnArgs(ctypes.Structure):
     ]
 
 
+class GatArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("rows", _i32p), ("n_rows", _i64),
+        ("items", _i32p), ("n_items", _i64), ("split", _i32p), ("n_split", _i64),
+        ("col", _i32p),
+        ("h_src", _f32p), ("ld_h", _i64),
+        ("a_src", _f32p), ("ld_as", _i64), ("a_dst", _f32p), ("ld_ad", _i64),
+        ("a_edge", _f32p), ("ld_ae", _i64), ("n_e", _i64), ("e_idx", _i32p),
+        ("heads", ctypes.c_int32), ("channels", ctypes.c_int32), ("negative_slope", _f32), ("drop_p", _f32),
+        ("bias", _f32p), ("out", _f32p), ("ld_out", _i64), ("partials", _f32p), ("stats", _f32p),
+        ("drop_key", _i32p), ("drop_seed", ctypes.c_uint64),
+    ]
+
+
+class GatBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("rows", _i32p), ("n_rows", _i64),
+        ("items", _i32p), ("n_items", _i64), ("split", _i32p), ("n_split", _i64), ("n_slots", _i64),
+        ("t_rowptr", _i32p), ("t_rows", _i32p), ("n_src", _i64),
+        ("t_items", _i32p), ("t_n_items", _i64), ("t_split", _i32p), ("t_n_split", _i64), ("t_n_slots", _i64),
+        ("t_col", _i32p), ("t_slot", _i32p), ("t_key", _i32p), ("t_e_idx", _i32p), ("n_kept", _i64),
+        ("h_src", _f32p), ("ld_h", _i64),
+        ("a_src", _f32p), ("ld_as", _i64), ("a_dst", _f32p), ("ld_ad", _i64),
+        ("a_edge", _f32p), ("ld_ae", _i64), ("n_e", _i64),
+        ("heads", ctypes.c_int32), ("channels", ctypes.c_int32), ("negative_slope", _f32), ("drop_p", _f32),
+        ("drop_seed", ctypes.c_uint64),
+        ("out", _f32p), ("ld_out", _i64), ("bias", _f32p), ("stats", _f32p),
+        ("grad_out", _f32p), ("ld_grad", _i64),
+        ("grad_h_src", _f32p), ("ld_gh", _i64), ("grad_a_src", _f32p), ("ld_gas", _i64),
+        ("grad_a_dst", _f32p), ("ld_gad", _i64), ("grad_a_edge", _f32p), ("ld_gae", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 # name -> argtypes (every entry point returns int unless listed in _RESTYPES)
 _SIGNATURES = {
     "kgx_version": [],
@@ -288,6 +324,9 @@ _SIGNATURES = {
     "kgx_gine_backward_run": [ctypes.POINTER(GineBackwardArgs), ctypes.c_void_p],
     "kgx_rgcn_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_rgcn_run": [ctypes.POINTER(RgcnArgs), ctypes.c_void_p],
+    "kgx_gat": [ctypes.POINTER(GatArgs), ctypes.c_void_p],
+    "kgx_gat_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_gat_backward": [ctypes.POINTER(GatBackwardArgs), ctypes.c_void_p],
     "kgx_negative_edges": [
         _i32p, _i32p, _i64, _i64, _i32p, _i32p, _i64, _int, ctypes.c_uint64, _int, _int,
         _i32p, _i64, _i32p, ctypes.c_void_p,

@@ -14,6 +14,7 @@ from .aggregators import (
 from .attention_pooling import AttentionPooling, Set2Set
 from .base import Dense, Layer, Sequential, set_random_seed
 from .decoders import DotProductDecoder
+from .gat_conv import GATConv
 from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
 from .gin_conv import GINConv
@@ -32,6 +33,7 @@ __all__ = [
     "BatchGlobalPooling",
     "Dense",
     "DotProductDecoder",
+    "GATConv",
     "GATv2Conv",
     "GCNConv",
     "GINConv",

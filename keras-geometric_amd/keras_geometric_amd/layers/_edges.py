@@ -85,3 +85,37 @@ def graph_for(
         return g
 
     return G.cached(key, edge_index_obj, build)
+
+
+def check_fill_value(layer: str, fill_value, edge_dim: int | None):
+    """fill_value of a layer with edge_dim and add_self_loops as the layers keep it: "mean", "add", a float
+    or an [edge_dim] tensor."""
+    if isinstance(fill_value, str):
+        if fill_value in ("max", "min", "mul"):
+            raise NotImplementedError(f"{layer}: fill_value {fill_value!r} is not implemented; use 'mean', "
+                                      "'add', a float or an [edge_dim] tensor")
+        if fill_value not in ("mean", "add"):
+            raise ValueError(f"{layer}: unknown fill_value {fill_value!r}")
+        return fill_value
+    if isinstance(fill_value, torch.Tensor):
+        if edge_dim is not None and tuple(fill_value.shape) != (edge_dim,):
+            raise ValueError(f"{layer}: a tensor fill_value must be [{edge_dim}], got {tuple(fill_value.shape)}")
+        return fill_value
+    return float(fill_value)
+
+
+def loop_attr(g: G.CSRGraph, edge_attr: torch.Tensor, fill, exact: bool) -> torch.Tensor:
+    """[n, edge_dim]: the edge_attr row of the self loop the graph added to every node (fill_value)."""
+    from .. import ops as kops
+
+    n, edge_dim = g.n_dst, edge_attr.shape[1]
+    if isinstance(fill, str):
+        # by-edge sum over the loop graph itself (no second CSR): its loop slots read the zero rows E + i
+        table = torch.cat([edge_attr, edge_attr.new_zeros((n, edge_dim))], dim=0)
+        tot = kops.aggregate(g, table, "sum", by_edge=True, exact=exact)
+        if fill == "add":
+            return tot
+        return tot / (g.deg.to(tot.dtype) - 1.0).clamp_min(1.0)[:, None]  # the loop-free in-degree
+    if isinstance(fill, torch.Tensor):
+        return fill.to(edge_attr).reshape(1, edge_dim).expand(n, -1)
+    return edge_attr.new_full((n, edge_dim), fill)

@@ -29,7 +29,7 @@ from typing import Any
 import torch
 
 from .. import ops as kops
-from ._edges import edge_index_tensor, graph_for
+from ._edges import check_fill_value, edge_index_tensor, graph_for, loop_attr
 from .base import Dense, to_device_tensor
 from .message_passing import MessagePassing
 
@@ -55,18 +55,7 @@ class GATv2Conv(MessagePassing):
         self.edge_dim = None if edge_dim is None else int(edge_dim)
         if self.edge_dim is not None and self.edge_dim <= 0:
             raise ValueError(f"GATv2Conv: edge_dim must be positive, got {edge_dim}")
-        if isinstance(fill_value, str):
-            if fill_value in ("max", "min", "mul"):
-                raise NotImplementedError(f"GATv2Conv: fill_value {fill_value!r} is not implemented; use 'mean', "
-                                          "'add', a float or an [edge_dim] tensor")
-            if fill_value not in ("mean", "add"):
-                raise ValueError(f"GATv2Conv: unknown fill_value {fill_value!r}")
-        elif isinstance(fill_value, torch.Tensor):
-            if self.edge_dim is not None and tuple(fill_value.shape) != (self.edge_dim,):
-                raise ValueError(f"GATv2Conv: a tensor fill_value must be [{self.edge_dim}], got "
-                                 f"{tuple(fill_value.shape)}")
-        else:
-            fill_value = float(fill_value)
+        fill_value = check_fill_value("GATv2Conv", fill_value, self.edge_dim)
         self.fill_value = fill_value
         self.output_dim = output_dim
         self.heads = heads
@@ -152,18 +141,7 @@ class GATv2Conv(MessagePassing):
 
     def _loop_attr(self, g, edge_attr):
         """[n, edge_dim]: the edge_attr row of the self loop the graph added to every node (fill_value)."""
-        n = g.n_dst
-        fill = self.fill_value
-        if isinstance(fill, str):
-            # by-edge sum over the loop graph itself (no second CSR): its loop slots read the zero rows E + i
-            table = torch.cat([edge_attr, edge_attr.new_zeros((n, self.edge_dim))], dim=0)
-            tot = kops.aggregate(g, table, "sum", by_edge=True, exact=self.exact)
-            if fill == "add":
-                return tot
-            return tot / (g.deg.to(tot.dtype) - 1.0).clamp_min(1.0)[:, None]  # the loop-free in-degree
-        if isinstance(fill, torch.Tensor):
-            return fill.to(edge_attr).reshape(1, self.edge_dim).expand(n, -1)
-        return edge_attr.new_full((n, self.edge_dim), fill)
+        return loop_attr(g, edge_attr, self.fill_value, self.exact)
 
     def _gatv2_propagate(self, x_i, x_j, ei, edge_index_obj, self_loops: bool | None = None, training=None,
                          edge_attr=None):

@@ -2884,3 +2884,338 @@ def rgcn_aggregate(rg, x: torch.Tensor, weight: torch.Tensor, root: torch.Tensor
         return _RgcnFn.apply(x, weight, root, bias, rg, aggr == "mean")
     out = torch.empty((rg.n_dst, F_out), dtype=torch.float32, device=x.device)
     return _timed(lambda: rgcn_into(out, rg, x, weight, root, bias, mean=aggr == "mean"))
+
+
+# ---------------------------------------------------------------------------
+# GAT: scalar-score graph attention (kgx_gat / kgx_gat_backward)
+# ---------------------------------------------------------------------------
+def gat_supported(heads: int, channels: int) -> bool:
+    """(heads, channels) whose row fits a group of 64 lanes (attn_pick_k of csrc/kgx_attn_layout.h for
+    aligned rows: 8, 4 or 16 channels per lane where they divide `channels`, else 2 or 1)."""
+    ks = [k for k in (8, 4, 16) if channels % k == 0] or [2 if channels % 2 == 0 else 1]
+    return heads > 0 and channels > 0 and any(
+        heads * (1 << ((channels + k - 1) // k - 1).bit_length()) <= 64 for k in ks)
+
+
+def _gat_rows(t: torch.Tensor, width: int, what: str) -> torch.Tensor:
+    """A [n, heads*channels] table kgx_gat reads in place (a column view of a wider table included); rows
+    whose address or stride would cost the kernel its vector width are copied."""
+    t = _attn_table(t, width, what, "gat")
+    ld = _attn_ld(t)
+    vec = 4 if width % 4 == 0 else (2 if width % 2 == 0 else 1)
+    return t.contiguous() if (t.data_ptr() % (4 * vec) or ld % vec) else t
+
+
+def _gat_operands(h_src, a_src, a_dst, bias, edge, edge_idx, heads, channels, n_slots_csr):
+    h_src = _gat_rows(h_src, heads * channels, "h_src")
+    a_src, a_dst = _attn_table(a_src, heads, "a_src", "gat"), _attn_table(a_dst, heads, "a_dst", "gat")
+    if edge is not None:
+        edge = _edge_table(edge, edge_idx, heads, n_slots_csr, "gat")
+    return h_src, a_src, a_dst, _f32c(bias), edge, (edge_idx if edge is not None else None)
+
+
+def _gat_impl(h_src, a_src, a_dst, rowptr, rows, items, split, col, heads, channels, negative_slope, bias, n_slots,
+              save_stats, drop_key, drop_p, drop_seed, edge, edge_idx):
+    h_src, a_src, a_dst, bias, edge, edge_idx = _gat_operands(h_src, a_src, a_dst, bias, edge, edge_idx, heads,
+                                                              channels, col.numel())
+    dev = nat.require_device(h_src, a_src, a_dst, rowptr, rows, col, bias, items, split, edge, edge_idx, drop_key)
+    n_dst = rowptr.numel() - 1
+    out = torch.empty((n_dst, heads * channels), dtype=torch.float32, device=dev)
+    stats = torch.empty((n_dst if save_stats else 0, 2 * heads), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return out, stats
+    n_items, n_split = _sched_counts(items, split)
+    partials = _attn_partials(dev, items, n_split, n_slots, heads, channels)
+    key, p, seed = (drop_key, float(drop_p), int(drop_seed) & (2**64 - 1)) if drop_p > 0 else (None, 0.0, 0)
+    a = nat.GatArgs(
+        struct_size=ctypes.sizeof(nat.GatArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows), n_rows=n_dst,
+        items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split, col=nat.addr(col),
+        h_src=nat.addr(h_src), ld_h=_attn_ld(h_src), a_src=nat.addr(a_src), ld_as=_attn_ld(a_src),
+        a_dst=nat.addr(a_dst), ld_ad=_attn_ld(a_dst), a_edge=nat.addr(edge),
+        ld_ae=_attn_ld(edge) if edge is not None else 0, n_e=edge.shape[0] if edge is not None else 0,
+        e_idx=nat.addr(edge_idx), heads=heads, channels=channels, negative_slope=float(negative_slope), drop_p=p,
+        bias=nat.addr(bias), out=nat.addr(out), ld_out=out.stride(0), partials=nat.addr(partials),
+        stats=nat.addr(stats) if save_stats else None, drop_key=nat.addr(key), drop_seed=seed,
+    )
+    nat.check(nat.lib().kgx_gat(ctypes.byref(a), nat.stream(dev)), "kgx_gat")
+    return out, stats
+
+
+@torch.library.custom_op("kgx::gat_save", mutates_args=())
+def gat_save(
+    h_src: torch.Tensor,
+    a_src: torch.Tensor,
+    a_dst: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    heads: int,
+    channels: int,
+    negative_slope: float,
+    bias: Optional[torch.Tensor],
+    n_slots: int,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """kgx::gat that also returns the per-row softmax statistics [n, 2*heads] (max, denominator)."""
+    return _gat_impl(h_src, a_src, a_dst, rowptr, rows, items, split, col, heads, channels, negative_slope, bias,
+                     n_slots, True, drop_key, drop_p, drop_seed, edge, edge_idx)
+
+
+@gat_save.register_fake
+def _gat_save_fake(h_src, a_src, a_dst, rowptr, rows, items, split, col, heads, channels, negative_slope, bias,
+                   n_slots, drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
+    n = rowptr.shape[0] - 1
+    return h_src.new_empty((n, heads * channels)), h_src.new_empty((n, 2 * heads))
+
+
+@torch.library.custom_op("kgx::gat", mutates_args=())
+def gat(
+    h_src: torch.Tensor,
+    a_src: torch.Tensor,
+    a_dst: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    heads: int,
+    channels: int,
+    negative_slope: float,
+    bias: Optional[torch.Tensor],
+    n_slots: int,
+    drop_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fused GAT attention aggregation (kgx_gat): scores leaky_relu((a_dst[i] + a_src[j]) + edge[e]) from the
+    scalar tables a_src [n_src, heads], a_dst [n_dst, heads] and edge [n_e, heads] (row edge_idx[slot], None:
+    the slot; a row outside the table counts as 0), softmax per destination, weighted sum of h_src rows."""
+    return _gat_impl(h_src, a_src, a_dst, rowptr, rows, items, split, col, heads, channels, negative_slope, bias,
+                     n_slots, False, drop_key, drop_p, drop_seed, edge, edge_idx)[0]
+
+
+@gat.register_fake
+def _gat_fake(h_src, a_src, a_dst, rowptr, rows, items, split, col, heads, channels, negative_slope, bias, n_slots,
+              drop_key=None, drop_p=0.0, drop_seed=0, edge=None, edge_idx=None):
+    return h_src.new_empty((rowptr.shape[0] - 1, heads * channels))
+
+
+@torch.library.custom_op("kgx::gat_backward", mutates_args=())
+def gat_backward(
+    grad_out: torch.Tensor,
+    h_src: torch.Tensor,
+    a_src: torch.Tensor,
+    a_dst: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    edge: Optional[torch.Tensor],
+    out: torch.Tensor,
+    stats: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    n_slots: int,
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_slot: torch.Tensor,
+    t_slots: int,
+    heads: int,
+    channels: int,
+    negative_slope: float,
+    t_edge_idx: Optional[torch.Tensor],
+    zero_grad_edge: bool,
+    t_key: Optional[torch.Tensor] = None,
+    drop_p: float = 0.0,
+    drop_seed: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_h_src, grad_a_src, grad_a_dst, grad_edge) of kgx::gat_save (kgx_gat_backward); grad_edge is
+    [0, heads] without an edge table; zero_grad_edge: some row of `edge` belongs to no kept slot."""
+    kept = t_col.numel()
+    h_src, a_src, a_dst, bias, edge, _ = _gat_operands(h_src, a_src, a_dst, bias, edge, t_edge_idx, heads, channels,
+                                                       kept)
+    grad_out, out, stats = _gat_rows(grad_out, heads * channels, "grad_out"), _f32c(out), _f32c(stats)
+    dev = nat.require_device(grad_out, h_src, a_src, a_dst, bias, edge, out, stats, rowptr, rows, items, split,
+                             t_rowptr, t_rows, t_items, t_split, t_col, t_slot, t_edge_idx, t_key)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    g_h, g_as, g_ad = new(n_src, heads * channels), new(n_src, heads), new(n_dst, heads)
+    n_e = edge.shape[0] if edge is not None else 0
+    g_e = (torch.zeros if zero_grad_edge or kept == 0 else torch.empty)((n_e, heads), dtype=torch.float32, device=dev)
+    if n_dst == 0 and n_src == 0:
+        return g_h, g_as, g_ad, g_e
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
+    nbytes = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_gat_backward_workspace_bytes(n_dst, kept, n_slots, t_slots, heads, channels,
+                                                         ctypes.byref(nbytes)), "kgx_gat_backward_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+    key, p, seed = (t_key, float(drop_p), int(drop_seed) & (2**64 - 1)) if drop_p > 0 else (None, 0.0, 0)
+    a = nat.GatBackwardArgs(
+        struct_size=ctypes.sizeof(nat.GatBackwardArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows), n_rows=n_dst,
+        items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split, n_slots=n_slots,
+        t_rowptr=nat.addr(t_rowptr), t_rows=nat.addr(t_rows), n_src=n_src, t_items=nat.addr(t_items),
+        t_n_items=t_n_items, t_split=nat.addr(t_split), t_n_split=t_n_split, t_n_slots=t_slots,
+        t_col=nat.addr(t_col), t_slot=nat.addr(t_slot), t_key=nat.addr(key),
+        t_e_idx=nat.addr(t_edge_idx) if edge is not None else None, n_kept=kept,
+        h_src=nat.addr(h_src), ld_h=_attn_ld(h_src), a_src=nat.addr(a_src), ld_as=_attn_ld(a_src),
+        a_dst=nat.addr(a_dst), ld_ad=_attn_ld(a_dst), a_edge=nat.addr(edge),
+        ld_ae=_attn_ld(edge) if edge is not None else 0, n_e=n_e, heads=heads, channels=channels,
+        negative_slope=float(negative_slope), drop_p=p, drop_seed=seed, out=nat.addr(out), ld_out=out.stride(0),
+        bias=nat.addr(bias), stats=nat.addr(stats), grad_out=nat.addr(grad_out), ld_grad=_attn_ld(grad_out),
+        grad_h_src=nat.addr(g_h), ld_gh=heads * channels, grad_a_src=nat.addr(g_as), ld_gas=heads,
+        grad_a_dst=nat.addr(g_ad), ld_gad=heads, grad_a_edge=nat.addr(g_e) if edge is not None else None,
+        ld_gae=heads, workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_gat_backward(ctypes.byref(a), nat.stream(dev)), "kgx_gat_backward")
+    return g_h, g_as, g_ad, g_e
+
+
+@gat_backward.register_fake
+def _gat_backward_fake(grad_out, h_src, a_src, a_dst, bias, edge, out, stats, rowptr, rows, items, split, n_slots,
+                       t_rowptr, t_rows, t_items, t_split, t_col, t_slot, t_slots, heads, channels, negative_slope,
+                       t_edge_idx, zero_grad_edge, t_key=None, drop_p=0.0, drop_seed=0):
+    n_src, n_dst = t_rowptr.shape[0] - 1, rowptr.shape[0] - 1
+    return (h_src.new_empty((n_src, heads * channels)), h_src.new_empty((n_src, heads)),
+            h_src.new_empty((n_dst, heads)), h_src.new_empty((0 if edge is None else edge.shape[0], heads)))
+
+
+def _gat_call(op, g, h_src, a_src, a_dst, heads, channels, negative_slope, bias, exact, drop_p, drop_seed, edge,
+              edge_order):
+    items, _, split, _, n_slots = g.work(exact)
+    return _timed(lambda: op(
+        h_src, a_src, a_dst, g.rowptr, g.rows, items, split, g.col, heads, channels, float(negative_slope), bias,
+        n_slots, g.eid if drop_p > 0 else None, float(drop_p), int(drop_seed),
+        edge, g.eid if edge is not None and edge_order == "input" else None,
+    ))
+
+
+class _GatFn(torch.autograd.Function):
+    """Autograd of the fused GAT aggregation: the forward keeps its inputs, its output and the per-row
+    softmax statistics; kgx_gat_backward recomputes every edge's weight from the scalar tables in one pass
+    over the transposed CSR (one row gather per edge) and sums d a_dst over the forward schedule."""
+
+    @staticmethod
+    def forward(ctx, h_src, a_src, a_dst, bias, edge, g, heads, channels, negative_slope, exact, drop_p, drop_seed,
+                edge_order):
+        ctx.g, ctx.heads, ctx.channels, ctx.slope, ctx.exact = g, heads, channels, float(negative_slope), exact
+        ctx.drop_p, ctx.drop_seed, ctx.edge_order = drop_p, drop_seed, edge_order
+        out, stats = _gat_call(torch.ops.kgx.gat_save, g, h_src, a_src, a_dst, heads, channels, negative_slope, bias,
+                               exact, drop_p, drop_seed, edge, edge_order)
+        ctx.save_for_backward(h_src, a_src, a_dst, bias, edge, out, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        h_src, a_src, a_dst, bias, edge, out, stats = ctx.saved_tensors
+        g = ctx.g
+        t = G.transpose(g)
+        items, _, split, _, n_slots = g.work(ctx.exact)
+        t_items, _, t_split, _, t_slots = t.work(ctx.exact)
+        by_input = ctx.edge_order == "input"
+        # input order: the rows of input edges the graph dropped belong to no kept slot and stay zero
+        n_loops = g.n_dst if g.flags & nat.CSR_SELF_LOOPS else 0
+        unwritten = edge is not None and by_input and g.kept - n_loops != g.n_input_edges
+        g_h, g_as, g_ad, g_e = _timed(lambda: torch.ops.kgx.gat_backward(
+            grad_out, h_src, a_src, a_dst, bias, edge, out, stats, g.rowptr, g.rows, items, split, n_slots,
+            t.rowptr, t.rows, t_items, t_split, t.col, _fwd_slot32(t), t_slots, ctx.heads, ctx.channels, ctx.slope,
+            None if edge is None else (t.eid if by_input else _fwd_slot32(t)), unwritten,
+            t.eid if ctx.drop_p > 0 else None, float(ctx.drop_p), int(ctx.drop_seed),
+        ))
+        g_bias = grad_out.sum(0) if ctx.needs_input_grad[3] else None
+        return (g_h, g_as, g_ad, g_bias, g_e if edge is not None else None) + (None,) * 8
+
+
+def _gat_composed(g, h_src, a_src, a_dst, heads, channels, negative_slope, bias, drop_p, drop_seed, edge, edge_order):
+    """The composed torch form (any device, any float dtype): gathered scalars, a segment softmax with [E, H]
+    intermediates, and an index_add of the [E, H, C] weighted rows."""
+    from . import graph as G
+
+    H, C, n_dst = heads, channels, g.n_dst
+    dst, src = G.row_of_slot(g).long(), g.col.long()
+    z = a_dst[dst] + a_src[src]
+    if edge is not None and edge.shape[0] > 0:
+        if edge_order == "input":  # slots whose edge id is past the table carry no feature
+            r = g.eid.long()
+            z = z + torch.where((r < edge.shape[0])[:, None], edge[r.clamp_max(edge.shape[0] - 1)],
+                                torch.zeros((), dtype=edge.dtype, device=edge.device))
+        else:
+            z = z + edge
+    s = torch.nn.functional.leaky_relu(z, negative_slope)
+    idx = dst[:, None].expand(-1, H)
+    mx = torch.full((n_dst, H), float("-inf"), dtype=s.dtype, device=s.device).scatter_reduce(
+        0, idx, s.detach(), "amax", include_self=True)
+    ex = torch.exp(s - mx[dst])
+    den = torch.zeros((n_dst, H), dtype=s.dtype, device=s.device).index_add(0, dst, ex)
+    alpha = ex / (den[dst] + 1e-16)
+    if drop_p > 0:
+        alpha = alpha * dropout_mask(drop_seed, drop_p, g.eid, H).to(alpha.dtype)
+    msg = alpha[:, :, None] * h_src.reshape(-1, H, C)[src]
+    out = torch.zeros((n_dst, H, C), dtype=msg.dtype, device=msg.device).index_add(0, dst, msg).reshape(n_dst, H * C)
+    return out if bias is None else out + bias
+
+
+def gat_aggregate(
+    g: CSRGraph,
+    h_src: torch.Tensor,
+    a_src: torch.Tensor,
+    a_dst: torch.Tensor,
+    heads: int,
+    channels: int,
+    negative_slope: float,
+    *,
+    bias: torch.Tensor | None = None,
+    exact: bool = False,
+    dropout: float = 0.0,
+    seed: int = 0,
+    edge: torch.Tensor | None = None,
+    edge_order: str = "input",
+    fused: bool = True,
+) -> torch.Tensor:
+    """GAT's attention aggregation (PyG's GATConv after its linear maps), one fused pass (kgx_gat):
+      z_e = (a_dst[i] + a_src[j]) + edge[e]   alpha = softmax over the in-edges of i (leaky_relu(z))
+      out[i,h,:] = sum_e alpha_e * h_src[j_e,h,:] (+ bias)
+    h_src [g.n_src, heads*channels]; a_src [g.n_src, heads], a_dst [g.n_dst, heads] and edge [n_e, heads] are
+    SCALAR tables (<h, att_src>, <h, att_dst>, <lin_edge(edge_attr), att_edge> per head).  All of them may be
+    column views of one wider table and are read in place.  Differentiable in h_src, a_src, a_dst, edge and
+    bias; no [E, heads] weight table is kept for the backward.
+
+    exact, dropout / seed and edge_order mean what they mean in gatv2_aggregate.  edge_order="input": row e is
+    input edge e (rows E + i: the self loop the graph added to node i); a table may stop early, and a slot
+    whose row it does not have scores with 0.  "csr": [g.kept, heads] in CSR slot order.
+
+    fused=False, CPU tensors and shapes that do not fit a row's 64 lanes (gat_supported) take the composed
+    torch form."""
+    if edge_order not in ("input", "csr"):
+        raise ValueError(f"gat: edge_order must be 'input' or 'csr', got {edge_order!r}")
+    hc = heads * channels
+    for t, shape, what in ((h_src, (g.n_src, hc), "h_src"), (a_src, (g.n_src, heads), "a_src"),
+                           (a_dst, (g.n_dst, heads), "a_dst")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"gat: {what} must be {list(shape)}, got {tuple(t.shape)}")
+    if edge is not None:
+        most = g.kept if edge_order == "csr" else g.n_input_edges + (g.n_dst if g.flags & nat.CSR_SELF_LOOPS else 0)
+        if edge.dim() != 2 or edge.shape[1] != heads or edge.shape[0] > most or (
+                edge_order == "csr" and edge.shape[0] != most):
+            raise ValueError(f"gat: edge in {edge_order} order must be [{'' if edge_order == 'csr' else '<= '}{most}, "
+                             f"{heads}], got {tuple(edge.shape)}")
+    if not fused or not h_src.is_cuda or h_src.dtype != torch.float32 or not gat_supported(heads, channels):
+        return _gat_composed(g, h_src, a_src, a_dst, heads, channels, negative_slope, bias, float(dropout), int(seed),
+                             edge, edge_order)
+    if _needs_grad(h_src, a_src, a_dst, bias, edge):
+        return _GatFn.apply(h_src, a_src, a_dst, bias, edge, g, heads, channels, negative_slope, exact,
+                            float(dropout), int(seed), edge_order)
+    return _gat_call(torch.ops.kgx.gat, g, h_src, a_src, a_dst, heads, channels, negative_slope, bias, exact,
+                     float(dropout), int(seed), edge, edge_order)
