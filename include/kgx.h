@@ -1277,6 +1277,69 @@ int kgx_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_kept, int64_t n_s
                                      int channels, size_t* bytes);
 int kgx_gat_backward(const kgx_gat_backward_args* a, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Gated sum: the per-channel edge gate of the residual gated graph convolution
+ * (gated.hip; no reference counterpart, PyG's ResGatedGraphConv after its linear
+ * maps).  For destination i, its CSR slots t with source j = col[t]:
+ *   z_t = (k[i] + q[j]) + edge[e_t]        s_t = 1 / (1 + expf(-z_t))   (per channel)
+ *   out[i] = (sum_t s_t * v[j]  + root[i]) + bias
+ * z is formed by these two rounded fp32 adds, in this order, in every kernel; s is
+ * exactly 1 and exactly 0 where expf saturates, never NaN for finite inputs.
+ * The schedule (rowptr .. n_split) and col are those of kgx_gat.  k, root
+ * [n_rows, F], q, v [n_src, F] and edge [n_e, F] are fp32 tables with their own
+ * leading dimensions (column views of wider tables are read in place); edge
+ * NULL: no edge term, else the edge row of slot t is e_idx[t] (e_idx NULL: t
+ * itself) and a row outside [0, n_e) counts as 0.  root, bias: NULL = absent.  A
+ * row without edges stores root + bias.  partials: [n_slots, F] floats for the
+ * chunks of the split rows (needed when n_split > 0), added in chunk order.
+ * F a multiple of 4 in [4, 512], every table 16-byte aligned with a leading
+ * dimension that is a multiple of 4 (read four floats at a time), else
+ * KGX_ERR_UNSUPPORTED before any device work; KGX_ERR_ARG with a message for a
+ * foreign struct_size, a null operand, a leading dimension below F or >= 2^31,
+ * n_e outside [0, 2^31).  n_rows == 0: KGX_OK, nothing launched.
+ *
+ * kgx_gated_backward recomputes s from k, q and edge in two passes; nothing
+ * but the inputs is read.  With G = grad_out and dz_t = G[i] * v[j] * s_t (1 - s_t):
+ *   pass 1, destination CSR:  grad_k[i] = sum_t dz_t,  grad_edge[e_t] = dz_t
+ *           (one writer per row; rows no slot names are not written)
+ *   pass 2, TRANSPOSED CSR (t_rowptr [n_src + 1] with its own schedule, t_col =
+ *           the slot's destination, t_e_idx = its edge row, required with edge):
+ *           grad_q[j] = sum_t dz_t,  grad_v[j] = sum_t s_t * G[i]
+ * n_slots / t_n_slots: the chunk slots of the two schedules.  workspace:
+ * kgx_gated_backward_workspace_bytes(n_slots, t_n_slots, F) bytes, 16-byte
+ * aligned.  No atomics: out and every gradient are the same bits from run to run.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_gated_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split;
+  const int32_t* col;
+  const float* k; int64_t ld_k; const float* q; int64_t ld_q; const float* v; int64_t ld_v;
+  const float* edge; int64_t ld_e; int64_t n_e; const int32_t* e_idx;
+  const float* root; int64_t ld_root; const float* bias;
+  int64_t F;
+  float* out; int64_t ld_out; float* partials;
+} kgx_gated_args;
+typedef struct kgx_gated_backward_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split; int64_t n_slots;
+  const int32_t* col; const int32_t* e_idx;
+  const int32_t* t_rowptr; const int32_t* t_rows; int64_t n_src;
+  const int32_t* t_items; int64_t t_n_items; const int32_t* t_split; int64_t t_n_split; int64_t t_n_slots;
+  const int32_t* t_col; const int32_t* t_e_idx;
+  const float* k; int64_t ld_k; const float* q; int64_t ld_q; const float* v; int64_t ld_v;
+  const float* edge; int64_t ld_e; int64_t n_e;
+  int64_t F;
+  const float* grad_out; int64_t ld_grad;
+  float* grad_k; int64_t ld_gk; float* grad_q; int64_t ld_gq; float* grad_v; int64_t ld_gv;
+  float* grad_edge; int64_t ld_ge;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_gated_backward_args;
+int kgx_gated(const kgx_gated_args* a, kgx_stream_t stream);
+int kgx_gated_backward_workspace_bytes(int64_t n_slots, int64_t t_n_slots, int64_t F, size_t* bytes);
+int kgx_gated_backward(const kgx_gated_backward_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from .layers import (
     GlobalPooling,
     MessagePassing,
     PNAConv,
+    ResGatedGraphConv,
     RGCNConv,
     SAGEConv,
     Set2Set,
@@ -51,6 +52,7 @@ __all__ = [
     "NeighborSampler",
     "PNAConv",
     "RGCNConv",
+    "ResGatedGraphConv",
     "SAGEConv",
     "SampledBlocks",
     "SampledSubgraph",

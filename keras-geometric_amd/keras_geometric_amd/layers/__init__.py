@@ -22,6 +22,7 @@ from .gine_conv import GINEConv
 from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
+from .resgated_conv import ResGatedGraphConv
 from .rgcn_conv import RGCNConv
 from .sage_conv import SAGEConv
 from .transformer_conv import TransformerConv
@@ -48,6 +49,7 @@ __all__ = [
     "PNAConv",
     "RGCNConv",
     "PoolingAggregator",
+    "ResGatedGraphConv",
     "SAGEConv",
     "Sequential",
     "Set2Set",

@@ -10,6 +10,7 @@ torch.compile / symbolic tracing sees shapes without running the GPU.
   kgx::dot_attention  fused dot-product (query / key / value) attention aggregation
   kgx::softmax_pool  fused segment softmax + weighted sum (attention readouts)
   kgx::edge_dot  edge scores from node rows (link prediction)
+  kgx::gated  fused per-channel edge gate (residual gated graph convolution)
   kgx::gather_rows, kgx::scatter_f32   row movement helpers
 """
 
@@ -3219,3 +3220,248 @@ def gat_aggregate(
                             float(dropout), int(seed), edge_order)
     return _gat_call(torch.ops.kgx.gat, g, h_src, a_src, a_dst, heads, channels, negative_slope, bias, exact,
                      float(dropout), int(seed), edge, edge_order)
+
+
+# ---------------------------------------------------------------------------
+# Gated sum: per-channel edge gate (kgx_gated / kgx_gated_backward)
+# ---------------------------------------------------------------------------
+def gated_supported(F: int) -> bool:
+    """Widths gated.hip implements: F a multiple of 4 in [4, 512]."""
+    return F % 4 == 0 and 4 <= F <= 512
+
+
+def _gated_rows(t: torch.Tensor, F: int, what: str) -> torch.Tensor:
+    """A [n, F] fp32 table kgx_gated reads in place, four floats at a time (a column view of a wider table
+    included); rows whose address or stride is not 16-byte aligned are copied."""
+    t = _attn_table(t, F, what, "gated")
+    return t.contiguous() if (t.data_ptr() % 16 or _attn_ld(t) % 4) else t
+
+
+def _gated_edge(edge, edge_idx, F, n_slots_csr):
+    if edge is None:
+        return None, None
+    edge = _edge_table(_gated_rows(edge, F, "edge"), edge_idx, F, n_slots_csr, "gated")
+    return edge, edge_idx
+
+
+@torch.library.custom_op("kgx::gated", mutates_args=())
+def gated(
+    k: torch.Tensor,
+    q: torch.Tensor,
+    v: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    edge: Optional[torch.Tensor] = None,
+    edge_idx: Optional[torch.Tensor] = None,
+    root: Optional[torch.Tensor] = None,
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fused gated sum (kgx_gated): out[i] = sum_{t into i} sigmoid((k[i] + q[col t]) + edge[e_t]) * v[col t]
+    + root[i] + bias; e_t = edge_idx[t], or t without edge_idx."""
+    F = k.shape[1]
+    k, q, v = _gated_rows(k, F, "k"), _gated_rows(q, F, "q"), _gated_rows(v, F, "v")
+    root = None if root is None else _gated_rows(root, F, "root")
+    edge, edge_idx = _gated_edge(edge, edge_idx, F, col.numel())
+    bias = _f32c(bias)
+    dev = nat.require_device(k, q, v, rowptr, rows, items, split, col, edge, edge_idx, root, bias)
+    n_dst = rowptr.numel() - 1
+    out = torch.empty((n_dst, F), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return out
+    n_items, n_split = _sched_counts(items, split)
+    partials = torch.empty((n_slots, F), dtype=torch.float32, device=dev) if items is not None and n_split else None
+    a = nat.GatedArgs(
+        struct_size=ctypes.sizeof(nat.GatedArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows), n_rows=n_dst,
+        items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split, col=nat.addr(col),
+        k=nat.addr(k), ld_k=_attn_ld(k), q=nat.addr(q), ld_q=_attn_ld(q), v=nat.addr(v), ld_v=_attn_ld(v),
+        edge=nat.addr(edge), ld_e=_attn_ld(edge) if edge is not None else 0,
+        n_e=edge.shape[0] if edge is not None else 0, e_idx=nat.addr(edge_idx),
+        root=nat.addr(root), ld_root=_attn_ld(root) if root is not None else 0, bias=nat.addr(bias), F=F,
+        out=nat.addr(out), ld_out=F, partials=nat.addr(partials),
+    )
+    nat.check(nat.lib().kgx_gated(ctypes.byref(a), nat.stream(dev)), "kgx_gated")
+    return out
+
+
+@gated.register_fake
+def _gated_fake(k, q, v, rowptr, rows, items, split, col, n_slots, edge=None, edge_idx=None, root=None, bias=None):
+    return k.new_empty((rowptr.shape[0] - 1, k.shape[1]))
+
+
+@torch.library.custom_op("kgx::gated_backward", mutates_args=())
+def gated_backward(
+    grad_out: torch.Tensor,
+    k: torch.Tensor,
+    q: torch.Tensor,
+    v: torch.Tensor,
+    edge: Optional[torch.Tensor],
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    edge_idx: Optional[torch.Tensor],
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_slots: int,
+    t_edge_idx: Optional[torch.Tensor],
+    zero_grad_edge: bool,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_k, grad_q, grad_v, grad_edge) of kgx::gated (kgx_gated_backward); grad_edge is [0, F] without an
+    edge table; zero_grad_edge: some row of `edge` belongs to no slot."""
+    F = k.shape[1]
+    k, q, v = _gated_rows(k, F, "k"), _gated_rows(q, F, "q"), _gated_rows(v, F, "v")
+    grad_out = _gated_rows(grad_out, F, "grad_out")
+    edge, edge_idx = _gated_edge(edge, edge_idx, F, col.numel())
+    dev = nat.require_device(grad_out, k, q, v, edge, rowptr, rows, items, split, col, edge_idx, t_rowptr, t_rows,
+                             t_items, t_split, t_col, t_edge_idx)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    new = lambda n: torch.empty((n, F), dtype=torch.float32, device=dev)  # noqa: E731
+    g_k, g_q, g_v = new(n_dst), new(n_src), new(n_src)
+    n_e = edge.shape[0] if edge is not None else 0
+    g_e = (torch.zeros if zero_grad_edge or col.numel() == 0 else torch.empty)((n_e, F), dtype=torch.float32,
+                                                                             device=dev)
+    if n_dst == 0 and n_src == 0:
+        return g_k, g_q, g_v, g_e
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
+    nbytes = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_gated_backward_workspace_bytes(n_slots, t_slots, F, ctypes.byref(nbytes)),
+              "kgx_gated_backward_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+    a = nat.GatedBackwardArgs(
+        struct_size=ctypes.sizeof(nat.GatedBackwardArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows), n_rows=n_dst,
+        items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split, n_slots=n_slots,
+        col=nat.addr(col), e_idx=nat.addr(edge_idx),
+        t_rowptr=nat.addr(t_rowptr), t_rows=nat.addr(t_rows), n_src=n_src, t_items=nat.addr(t_items),
+        t_n_items=t_n_items, t_split=nat.addr(t_split), t_n_split=t_n_split, t_n_slots=t_slots,
+        t_col=nat.addr(t_col), t_e_idx=nat.addr(t_edge_idx) if edge is not None else None,
+        k=nat.addr(k), ld_k=_attn_ld(k), q=nat.addr(q), ld_q=_attn_ld(q), v=nat.addr(v), ld_v=_attn_ld(v),
+        edge=nat.addr(edge), ld_e=_attn_ld(edge) if edge is not None else 0, n_e=n_e, F=F,
+        grad_out=nat.addr(grad_out), ld_grad=_attn_ld(grad_out), grad_k=nat.addr(g_k), ld_gk=F,
+        grad_q=nat.addr(g_q), ld_gq=F, grad_v=nat.addr(g_v), ld_gv=F,
+        grad_edge=nat.addr(g_e) if edge is not None else None, ld_ge=F,
+        workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_gated_backward(ctypes.byref(a), nat.stream(dev)), "kgx_gated_backward")
+    return g_k, g_q, g_v, g_e
+
+
+@gated_backward.register_fake
+def _gated_backward_fake(grad_out, k, q, v, edge, rowptr, rows, items, split, col, n_slots, edge_idx, t_rowptr,
+                         t_rows, t_items, t_split, t_col, t_slots, t_edge_idx, zero_grad_edge):
+    n_src, F = t_rowptr.shape[0] - 1, k.shape[1]
+    return (k.new_empty((rowptr.shape[0] - 1, F)), k.new_empty((n_src, F)), k.new_empty((n_src, F)),
+            k.new_empty((0 if edge is None else edge.shape[0], F)))
+
+
+def _gated_raw(g, k, q, v, edge, edge_order, root, bias, exact):
+    items, _, split, _, n_slots = g.work(exact)
+    return _timed(lambda: torch.ops.kgx.gated(
+        k, q, v, g.rowptr, g.rows, items, split, g.col, n_slots, edge,
+        g.eid if edge is not None and edge_order == "input" else None, root, bias))
+
+
+class _GatedFn(torch.autograd.Function):
+    """Autograd of the fused gated sum: nothing but the inputs is kept; kgx_gated_backward recomputes every
+    gate in one pass over the destination CSR (d k, d edge) and one over the transposed CSR (d q, d v)."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, edge, root, bias, g, exact, edge_order):
+        ctx.g, ctx.exact, ctx.edge_order = g, exact, edge_order
+        ctx.save_for_backward(k, q, v, edge)
+        return _gated_raw(g, k, q, v, edge, edge_order, root, bias, exact)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        k, q, v, edge = ctx.saved_tensors
+        g = ctx.g
+        t = G.transpose(g)
+        items, _, split, _, n_slots = g.work(ctx.exact)
+        t_items, _, t_split, _, t_slots = t.work(ctx.exact)
+        by_input = ctx.edge_order == "input"
+        # input order: the rows of input edges the graph dropped belong to no slot and stay zero
+        unwritten = edge is not None and by_input and g.kept != g.n_input_edges
+        g_k, g_q, g_v, g_e = _timed(lambda: torch.ops.kgx.gated_backward(
+            grad_out, k, q, v, edge, g.rowptr, g.rows, items, split, g.col, n_slots,
+            g.eid if edge is not None and by_input else None, t.rowptr, t.rows, t_items, t_split, t.col, t_slots,
+            None if edge is None else (t.eid if by_input else _fwd_slot32(t)), unwritten))
+        g_root = grad_out if ctx.needs_input_grad[4] else None
+        g_bias = grad_out.sum(0) if ctx.needs_input_grad[5] else None
+        return g_k, g_q, g_v, (g_e if edge is not None else None), g_root, g_bias, None, None, None
+
+
+def _gated_composed(g, k, q, v, edge, edge_order, root, bias):
+    """The composed torch form (any device, any float dtype): [kept, F] gathered rows, gates and messages,
+    summed by index_add."""
+    from . import graph as G
+
+    dst, src = G.row_of_slot(g).long(), g.col.long()
+    z = k[dst] + q[src]
+    if edge is not None:
+        z = z + (edge[g.eid.long()] if edge_order == "input" else edge)
+    msg = torch.sigmoid(z) * v[src]
+    out = torch.zeros((g.n_dst, k.shape[1]), dtype=msg.dtype, device=msg.device).index_add(0, dst, msg)
+    if root is not None:
+        out = out + root
+    return out if bias is None else out + bias
+
+
+def gated_aggregate(
+    g: CSRGraph,
+    k: torch.Tensor,
+    q: torch.Tensor,
+    v: torch.Tensor,
+    *,
+    edge: torch.Tensor | None = None,
+    edge_order: str = "input",
+    root: torch.Tensor | None = None,
+    bias: torch.Tensor | None = None,
+    exact: bool = False,
+    fused: bool = True,
+) -> torch.Tensor:
+    """The residual gated graph convolution's aggregation (PyG's ResGatedGraphConv after its linear maps), one
+    fused pass (kgx_gated):
+      out[i] = sum_{j -> i} sigmoid((k[i] + q[j]) + edge[e]) * v[j]  + root[i] + bias     (a gate per channel)
+    k, root [g.n_dst, F]; q, v [g.n_src, F]; bias [F].  All of them may be column views of one wider table and
+    are read in place.  Differentiable in every one of them; the backward recomputes the gates, so no [E, F]
+    tensor is written or kept in either direction.
+
+    edge_order="input": edge is [g.n_input_edges, F], row e the input edge e (the rows of edges the graph
+    dropped get a zero gradient); "csr": [g.kept, F] in CSR slot order.  exact means what it means in
+    gat_aggregate: hub rows are summed whole, in CSR order.
+
+    fused=False, CPU tensors, non-fp32 inputs, a graph without edges and widths outside gated_supported take
+    the composed torch form."""
+    if edge_order not in ("input", "csr"):
+        raise ValueError(f"gated: edge_order must be 'input' or 'csr', got {edge_order!r}")
+    if k.dim() != 2 or k.shape[0] != g.n_dst:
+        raise ValueError(f"gated: k must be [{g.n_dst}, F], got {tuple(k.shape)}")
+    F = k.shape[1]
+    for t, shape, what in ((q, (g.n_src, F), "q"), (v, (g.n_src, F), "v"), (root, (g.n_dst, F), "root"),
+                           (bias, (F,), "bias")):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"gated: {what} must be {list(shape)}, got {tuple(t.shape)}")
+    if edge is not None:
+        if g.flags & nat.CSR_SELF_LOOPS:
+            raise ValueError("gated: the graph has added self-loop slots, which carry no edge feature; build it "
+                             "without")
+        n_e = g.kept if edge_order == "csr" else g.n_input_edges
+        if tuple(edge.shape) != (n_e, F):
+            raise ValueError(f"gated: edge in {edge_order} order must be [{n_e}, {F}], got {tuple(edge.shape)}")
+    if (not fused or not k.is_cuda or g.kept == 0 or not gated_supported(F)
+            or any(t is not None and t.dtype != torch.float32 for t in (k, q, v, edge, root, bias))):
+        return _gated_composed(g, k, q, v, edge, edge_order, root, bias)
+    if _needs_grad(k, q, v, edge, root, bias):
+        return _GatedFn.apply(k, q, v, edge, root, bias, g, exact, edge_order)
+    return _gated_raw(g, k, q, v, edge, edge_order, root, bias, exact)
