@@ -1340,6 +1340,78 @@ int kgx_gated(const kgx_gated_args* a, kgx_stream_t stream);
 int kgx_gated_backward_workspace_bytes(int64_t n_slots, int64_t t_n_slots, int64_t F, size_t* bytes);
 int kgx_gated_backward(const kgx_gated_backward_args* a, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Softmax aggregation: the per-channel learnable aggregation of DeeperGCN
+ * (softmax_aggr.hip; no reference counterpart, PyG's SoftmaxAggregation and the
+ * aggregation of GENConv).  For destination i, its CSR slots t with source
+ * j = col[t] and edge row e_t = e_idx[t] (e_idx NULL: t itself):
+ *   r_t = x[j] + edge[e_t]                 (one rounded fp32 add, the same in every kernel)
+ *   m_t = r_t  (KGX_SOFTMAX_MSG_IDENTITY)  or  max(r_t, 0) + eps  (KGX_SOFTMAX_MSG_GEN)
+ *   s_t = temp[c] * m_t      M = max_t s_t      S = sum_t exp(s_t - M)
+ *   out[i] = (sum_t exp(s_t - M) * m_t) / S                  (per channel c)
+ * x [n_src, F] or edge [n_e, F] may be NULL, not both: without x the edge rows are
+ * the messages themselves ("by edge") and col is not read.  An edge row outside
+ * [0, n_e) counts as 0.  temp [F] is a device vector of any finite values (0: the
+ * mean; negative: a soft minimum).  A row without slots stores zeros.  The
+ * schedule (rowptr .. n_split) and col are those of kgx_gat.  stats (NULL: not
+ * kept): per row M | S, and with stats_q != 0 also Q = sum_t p_t m_t^2, from which
+ * grad_temp = sum_i grad_out (Q - out^2); ld_stats >= 2F or 3F.  partials:
+ * [n_slots, 4F] floats for the chunks of the split rows (needed when n_split > 0),
+ * merged in chunk order.  The running sums are fp64.  F a multiple of 4 in
+ * [4, 512], every table 16-byte aligned with a leading dimension that is a multiple
+ * of 4, else KGX_ERR_UNSUPPORTED before any device work; KGX_ERR_ARG with a
+ * message for a foreign struct_size, x and edge both absent, a null temp or out,
+ * a leading dimension below the table's width or >= 2^31, n_e outside [0, 2^31).
+ * n_rows == 0: KGX_OK, nothing launched.
+ *
+ * kgx_softmax_aggr_backward recomputes every weight from x, edge, temp, out and
+ * stats (M | S).  With g = grad_out, p_t = exp(s_t - M) / S:
+ *   d r_t = g[i] p_t (1 + temp (m_t - out[i])),  0 where the GEN message has r_t <= 0
+ *   destination CSR (with an edge table):  grad_edge[e_t] = d r_t  (one writer per
+ *           row; rows no slot names are not written)
+ *   TRANSPOSED CSR (with x; t_rowptr [n_src + 1] with its own schedule, t_col = the
+ *           slot's destination, t_e_idx = its edge row, required with edge):
+ *           grad_x[j] = sum_t d r_t  (fp64 sums; split rows' chunks added in order)
+ * workspace: kgx_softmax_aggr_backward_workspace_bytes(n_rows, t_n_slots, F) bytes,
+ * 16-byte aligned (the packed destination rows g / S | M | 1 - temp out and the
+ * transposed chunks' partials).  No atomics: the same bits from run to run.
+ * ------------------------------------------------------------------------- */
+#define KGX_SOFTMAX_MSG_IDENTITY 0
+#define KGX_SOFTMAX_MSG_GEN 1
+typedef struct kgx_softmax_aggr_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split;
+  const int32_t* col;
+  const float* x; int64_t ld_x;
+  const float* edge; int64_t ld_e; int64_t n_e; const int32_t* e_idx;
+  const float* temp; int32_t message; float eps;
+  int64_t F;
+  float* out; int64_t ld_out;
+  float* stats; int64_t ld_stats; int64_t stats_q;
+  float* partials;
+} kgx_softmax_aggr_args;
+typedef struct kgx_softmax_aggr_backward_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* rows; int64_t n_rows;
+  const int32_t* items; int64_t n_items; const int32_t* split; int64_t n_split;
+  const int32_t* col; const int32_t* e_idx;
+  const int32_t* t_rowptr; const int32_t* t_rows; int64_t n_src;
+  const int32_t* t_items; int64_t t_n_items; const int32_t* t_split; int64_t t_n_split; int64_t t_n_slots;
+  const int32_t* t_col; const int32_t* t_e_idx;
+  const float* x; int64_t ld_x;
+  const float* edge; int64_t ld_e; int64_t n_e;
+  const float* temp; int32_t message; float eps;
+  int64_t F;
+  const float* out; int64_t ld_out; const float* stats; int64_t ld_stats;
+  const float* grad_out; int64_t ld_grad;
+  float* grad_x; int64_t ld_gx; float* grad_edge; int64_t ld_ge;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_softmax_aggr_backward_args;
+int kgx_softmax_aggr(const kgx_softmax_aggr_args* a, kgx_stream_t stream);
+int kgx_softmax_aggr_backward_workspace_bytes(int64_t n_rows, int64_t t_n_slots, int64_t F, size_t* bytes);
+int kgx_softmax_aggr_backward(const kgx_softmax_aggr_backward_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

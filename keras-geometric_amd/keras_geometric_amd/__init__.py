@@ -15,6 +15,7 @@ from .layers import (
     GATConv,
     GATv2Conv,
     GCNConv,
+    GENConv,
     GINConv,
     GINEConv,
     GlobalPooling,
@@ -43,6 +44,7 @@ __all__ = [
     "GATConv",
     "GATv2Conv",
     "GCNConv",
+    "GENConv",
     "GINConv",
     "GINEConv",
     "GlobalPooling",

@@ -189,6 +189,45 @@ class GatedBackwardArgs(ctypes.Structure):
     ]
 
 
+SOFTMAX_MSG = {"identity": 0, "gen": 1}  # KGX_SOFTMAX_MSG_*
+
+
+class SoftmaxAggrArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("rows", _i32p), ("n_rows", _i64),
+        ("items", _i32p), ("n_items", _i64), ("split", _i32p), ("n_split", _i64),
+        ("col", _i32p),
+        ("x", _f32p), ("ld_x", _i64),
+        ("edge", _f32p), ("ld_e", _i64), ("n_e", _i64), ("e_idx", _i32p),
+        ("temp", _f32p), ("message", ctypes.c_int32), ("eps", _f32),
+        ("F", _i64),
+        ("out", _f32p), ("ld_out", _i64),
+        ("stats", _f32p), ("ld_stats", _i64), ("stats_q", _i64),
+        ("partials", _f32p),
+    ]
+
+
+class SoftmaxAggrBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("rows", _i32p), ("n_rows", _i64),
+        ("items", _i32p), ("n_items", _i64), ("split", _i32p), ("n_split", _i64),
+        ("col", _i32p), ("e_idx", _i32p),
+        ("t_rowptr", _i32p), ("t_rows", _i32p), ("n_src", _i64),
+        ("t_items", _i32p), ("t_n_items", _i64), ("t_split", _i32p), ("t_n_split", _i64), ("t_n_slots", _i64),
+        ("t_col", _i32p), ("t_e_idx", _i32p),
+        ("x", _f32p), ("ld_x", _i64),
+        ("edge", _f32p), ("ld_e", _i64), ("n_e", _i64),
+        ("temp", _f32p), ("message", ctypes.c_int32), ("eps", _f32),
+        ("F", _i64),
+        ("out", _f32p), ("ld_out", _i64), ("stats", _f32p), ("ld_stats", _i64),
+        ("grad_out", _f32p), ("ld_grad", _i64),
+        ("grad_x", _f32p), ("ld_gx", _i64), ("grad_edge", _f32p), ("ld_ge", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 # name -> argtypes (every entry point returns int unless listed in _RESTYPES)
 _SIGNATURES = {
     "kgx_version": [],
@@ -363,6 +402,9 @@ _SIGNATURES = {
     "kgx_gated": [ctypes.POINTER(GatedArgs), ctypes.c_void_p],
     "kgx_gated_backward_workspace_bytes": [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_gated_backward": [ctypes.POINTER(GatedBackwardArgs), ctypes.c_void_p],
+    "kgx_softmax_aggr": [ctypes.POINTER(SoftmaxAggrArgs), ctypes.c_void_p],
+    "kgx_softmax_aggr_backward_workspace_bytes": [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_softmax_aggr_backward": [ctypes.POINTER(SoftmaxAggrBackwardArgs), ctypes.c_void_p],
     "kgx_negative_edges": [
         _i32p, _i32p, _i64, _i64, _i32p, _i32p, _i64, _int, ctypes.c_uint64, _int, _int,
         _i32p, _i64, _i32p, ctypes.c_void_p,

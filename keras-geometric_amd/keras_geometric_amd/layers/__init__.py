@@ -8,6 +8,7 @@ from .aggregators import (
     MinAggregator,
     MultiAggregator,
     PoolingAggregator,
+    SoftmaxAggregator,
     StdAggregator,
     SumAggregator,
 )
@@ -17,6 +18,7 @@ from .decoders import DotProductDecoder
 from .gat_conv import GATConv
 from .gatv2_conv import GATv2Conv
 from .gcn_conv import GCNConv
+from .gen_conv import GENConv
 from .gin_conv import GINConv
 from .gine_conv import GINEConv
 from .message_passing import MessagePassing
@@ -37,6 +39,7 @@ __all__ = [
     "GATConv",
     "GATv2Conv",
     "GCNConv",
+    "GENConv",
     "GINConv",
     "GINEConv",
     "GlobalPooling",
@@ -53,6 +56,7 @@ __all__ = [
     "SAGEConv",
     "Sequential",
     "Set2Set",
+    "SoftmaxAggregator",
     "StdAggregator",
     "SumAggregator",
     "TransformerConv",

@@ -167,6 +167,29 @@ class MultiAggregator(Aggregator):
         return "+".join(self.names)
 
 
+class SoftmaxAggregator(Aggregator):
+    """The softmax aggregation of DeeperGCN (PyG's SoftmaxAggregation; no reference counterpart): per channel,
+    sum_t softmax_t(t * m_t) * m_t over a destination's messages.  t is a float, or a tensor (an nn.Parameter
+    to learn it), scalar or one value per channel.  One fused kgx_softmax_aggr pass; it has no registry name
+    (AggregatorFactory.create_softmax, or pass the instance to MessagePassing)."""
+
+    reduce = "softmax"
+
+    def __init__(self, t=1.0) -> None:
+        self.t = t
+
+    def _reduce(self, graph: CSRGraph, messages: torch.Tensor, exact: bool) -> torch.Tensor:
+        return kops.softmax_aggregate(graph, None, self.t, edge=messages, exact=exact)  # by-edge messages
+
+    def aggregate_nodes(self, graph: CSRGraph, x: torch.Tensor, exact: bool) -> torch.Tensor:
+        """The default message x_j without its [E, F] gather: the kernel's node-row form."""
+        return kops.softmax_aggregate(graph, x, self.t, exact=exact)
+
+    @property
+    def name(self) -> str:
+        return "softmax"
+
+
 class AggregatorFactory:
     """Registry (aggregators.py:281-343)."""
 
@@ -192,6 +215,10 @@ class AggregatorFactory:
     @classmethod
     def create_pooling(cls, pool_mlp) -> PoolingAggregator:
         return PoolingAggregator(pool_mlp)
+
+    @classmethod
+    def create_softmax(cls, t=1.0) -> SoftmaxAggregator:
+        return SoftmaxAggregator(t)
 
     @classmethod
     def get_available_aggregators(cls) -> list[str]:

@@ -24,9 +24,13 @@ from .base import Layer, to_device_tensor
 
 
 class MessagePassing(Layer):
-    def __init__(self, aggregator: str | list[str] = "mean", exact: bool | None = None, **kwargs) -> None:
+    def __init__(self, aggregator: str | list[str] | Aggregator = "mean", exact: bool | None = None, **kwargs) -> None:
         super().__init__(**kwargs)
-        if isinstance(aggregator, (list, tuple)):
+        if isinstance(aggregator, Aggregator):
+            # an aggregator that has no registry name (SoftmaxAggregator, PoolingAggregator); the config keeps its name
+            self._aggregator = aggregator
+            self.aggregator_name = self.aggregator = aggregator.name
+        elif isinstance(aggregator, (list, tuple)):
             # several aggregators of one neighbourhood, concatenated: [N, R * F] (no reference counterpart)
             self._aggregator: Aggregator = AggregatorFactory.create_multi(aggregator)
             self.aggregator_name = self._aggregator.name
@@ -90,9 +94,12 @@ class MessagePassing(Layer):
             return torch.zeros((n_dst, width), dtype=x_i.dtype, device=x_i.device)
         g = graph_for(edge_index, ei, n_src, n_dst, n_features=x_j.shape[1])
 
-        if edge_attr is None and self._fusable() and isinstance(self.aggregator, list):
+        named = self._aggregator.name in self.supported_aggregators or isinstance(self.aggregator, list)
+        if edge_attr is None and self._fusable() and hasattr(self._aggregator, "aggregate_nodes"):
+            aggregated = self._aggregator.aggregate_nodes(g, x_j.contiguous(), self.exact)
+        elif edge_attr is None and self._fusable() and isinstance(self.aggregator, list):
             aggregated = kops.multi_aggregate(g, x_j.contiguous(), self.aggregator, exact=self.exact)
-        elif edge_attr is None and self._fusable():
+        elif edge_attr is None and self._fusable() and named:
             aggregated = kops.aggregate(g, x_j.contiguous(), self._aggregator.reduce, exact=self.exact)
         else:
             # generic path: user hooks on per-edge tensors (indices validated by the CSR build)

@@ -3465,3 +3465,279 @@ def gated_aggregate(
     if _needs_grad(k, q, v, edge, root, bias):
         return _GatedFn.apply(k, q, v, edge, root, bias, g, exact, edge_order)
     return _gated_raw(g, k, q, v, edge, edge_order, root, bias, exact)
+
+
+# ---------------------------------------------------------------------------
+# Softmax aggregation: per-channel softmax over a row's slots (kgx_softmax_aggr / kgx_softmax_aggr_backward)
+# ---------------------------------------------------------------------------
+def softmax_aggr_supported(F: int) -> bool:
+    """Widths softmax_aggr.hip implements: F a multiple of 4 in [4, 512]."""
+    return F % 4 == 0 and 4 <= F <= 512
+
+
+def _softmax_rows(t: Optional[torch.Tensor], F: int, what: str) -> Optional[torch.Tensor]:
+    """A [n, F] fp32 table the kernels read in place four floats at a time (copied when not 16-byte aligned)."""
+    if t is None:
+        return None
+    t = _attn_table(t, F, what, "softmax_aggr")
+    return t.contiguous() if (t.data_ptr() % 16 or _attn_ld(t) % 4) else t
+
+
+def _softmax_operands(x, edge, edge_idx, temp, n_slots_csr):
+    F = (x if x is not None else edge).shape[1]
+    x, edge = _softmax_rows(x, F, "x"), _softmax_rows(edge, F, "edge")
+    if edge is not None:
+        edge = _edge_table(edge, edge_idx, F, n_slots_csr, "softmax_aggr")
+    temp = _f32c(temp)
+    if tuple(temp.shape) != (F,):
+        raise ValueError(f"softmax_aggr: temp must be [{F}], got {tuple(temp.shape)}")
+    return F, x, edge, (edge_idx if edge is not None else None), temp
+
+
+@torch.library.custom_op("kgx::softmax_aggr", mutates_args=())
+def softmax_aggr(
+    x: Optional[torch.Tensor],
+    edge: Optional[torch.Tensor],
+    temp: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    n_slots: int,
+    edge_idx: Optional[torch.Tensor] = None,
+    message: int = 0,
+    eps: float = 1e-7,
+    stats_cols: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Fused softmax aggregation (kgx_softmax_aggr): out[i] = sum_t softmax_t(temp * m_t) * m_t per channel,
+    m_t the message of x[col t] + edge[e_t] (x or edge may be None).  Returns (out, stats): stats is
+    [n_dst, stats_cols * F], M | S with stats_cols 2, M | S | Q with 3, empty with 0."""
+    F, x, edge, edge_idx, temp = _softmax_operands(x, edge, edge_idx, temp, col.numel())
+    dev = nat.require_device(x, edge, temp, rowptr, rows, items, split, col, edge_idx)
+    n_dst = rowptr.numel() - 1
+    out = torch.empty((n_dst, F), dtype=torch.float32, device=dev)
+    stats = torch.empty((n_dst, stats_cols * F), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return out, stats
+    n_items, n_split = _sched_counts(items, split)
+    partials = torch.empty((n_slots, 4 * F), dtype=torch.float32, device=dev) if items is not None and n_split else None
+    a = nat.SoftmaxAggrArgs(
+        struct_size=ctypes.sizeof(nat.SoftmaxAggrArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows), n_rows=n_dst,
+        items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split, col=nat.addr(col),
+        x=nat.addr(x), ld_x=_attn_ld(x) if x is not None else 0,
+        edge=nat.addr(edge), ld_e=_attn_ld(edge) if edge is not None else 0,
+        n_e=edge.shape[0] if edge is not None else 0, e_idx=nat.addr(edge_idx),
+        temp=nat.addr(temp), message=message, eps=eps, F=F, out=nat.addr(out), ld_out=F,
+        stats=nat.addr(stats) if stats_cols else None, ld_stats=stats_cols * F, stats_q=int(stats_cols == 3),
+        partials=nat.addr(partials),
+    )
+    nat.check(nat.lib().kgx_softmax_aggr(ctypes.byref(a), nat.stream(dev)), "kgx_softmax_aggr")
+    return out, stats
+
+
+@softmax_aggr.register_fake
+def _softmax_aggr_fake(x, edge, temp, rowptr, rows, items, split, col, n_slots, edge_idx=None, message=0, eps=1e-7,
+                       stats_cols=0):
+    n, F = rowptr.shape[0] - 1, temp.shape[0]
+    return temp.new_empty((n, F)), temp.new_empty((n, stats_cols * F))
+
+
+@torch.library.custom_op("kgx::softmax_aggr_backward", mutates_args=())
+def softmax_aggr_backward(
+    grad_out: torch.Tensor,
+    x: Optional[torch.Tensor],
+    edge: Optional[torch.Tensor],
+    temp: torch.Tensor,
+    out: torch.Tensor,
+    stats: torch.Tensor,
+    rowptr: torch.Tensor,
+    rows: torch.Tensor,
+    items: Optional[torch.Tensor],
+    split: Optional[torch.Tensor],
+    col: torch.Tensor,
+    edge_idx: Optional[torch.Tensor],
+    t_rowptr: torch.Tensor,
+    t_rows: torch.Tensor,
+    t_items: Optional[torch.Tensor],
+    t_split: Optional[torch.Tensor],
+    t_col: torch.Tensor,
+    t_slots: int,
+    t_edge_idx: Optional[torch.Tensor],
+    message: int,
+    eps: float,
+    zero_grad_edge: bool,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """(grad_x, grad_edge) of kgx::softmax_aggr (kgx_softmax_aggr_backward); each is [0, F] for an absent
+    operand; zero_grad_edge: some row of `edge` belongs to no slot."""
+    F, x, edge, edge_idx, temp = _softmax_operands(x, edge, edge_idx, temp, col.numel())
+    grad_out, out = _softmax_rows(grad_out, F, "grad_out"), _softmax_rows(out, F, "out")
+    stats = _f32c(stats)
+    dev = nat.require_device(grad_out, x, edge, temp, out, stats, rowptr, rows, items, split, col, edge_idx, t_rowptr,
+                             t_rows, t_items, t_split, t_col, t_edge_idx)
+    n_dst, n_src = rowptr.numel() - 1, t_rowptr.numel() - 1
+    n_e = edge.shape[0] if edge is not None else 0
+    empty = n_dst == 0 or col.numel() == 0
+    g_x = (torch.zeros if empty else torch.empty)((n_src if x is not None else 0, F), dtype=torch.float32, device=dev)
+    g_e = (torch.zeros if zero_grad_edge or empty else torch.empty)((n_e, F), dtype=torch.float32, device=dev)
+    if empty:
+        return g_x, g_e
+    n_items, n_split = _sched_counts(items, split)
+    t_n_items, t_n_split = _sched_counts(t_items, t_split)
+    nbytes = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_softmax_aggr_backward_workspace_bytes(n_dst, t_slots, F, ctypes.byref(nbytes)),
+              "kgx_softmax_aggr_backward_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+    a = nat.SoftmaxAggrBackwardArgs(
+        struct_size=ctypes.sizeof(nat.SoftmaxAggrBackwardArgs), rowptr=nat.addr(rowptr), rows=nat.addr(rows),
+        n_rows=n_dst, items=nat.addr(items), n_items=n_items, split=nat.addr(split), n_split=n_split,
+        col=nat.addr(col), e_idx=nat.addr(edge_idx),
+        t_rowptr=nat.addr(t_rowptr), t_rows=nat.addr(t_rows), n_src=n_src, t_items=nat.addr(t_items),
+        t_n_items=t_n_items, t_split=nat.addr(t_split), t_n_split=t_n_split, t_n_slots=t_slots,
+        t_col=nat.addr(t_col), t_e_idx=nat.addr(t_edge_idx) if edge is not None else None,
+        x=nat.addr(x), ld_x=_attn_ld(x) if x is not None else 0,
+        edge=nat.addr(edge), ld_e=_attn_ld(edge) if edge is not None else 0, n_e=n_e,
+        temp=nat.addr(temp), message=message, eps=eps, F=F,
+        out=nat.addr(out), ld_out=_attn_ld(out), stats=nat.addr(stats), ld_stats=stats.shape[1],
+        grad_out=nat.addr(grad_out), ld_grad=_attn_ld(grad_out),
+        grad_x=nat.addr(g_x) if x is not None else None, ld_gx=F,
+        grad_edge=nat.addr(g_e) if edge is not None else None, ld_ge=F,
+        workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_softmax_aggr_backward(ctypes.byref(a), nat.stream(dev)), "kgx_softmax_aggr_backward")
+    return g_x, g_e
+
+
+@softmax_aggr_backward.register_fake
+def _softmax_aggr_backward_fake(grad_out, x, edge, temp, out, stats, rowptr, rows, items, split, col, edge_idx,
+                                t_rowptr, t_rows, t_items, t_split, t_col, t_slots, t_edge_idx, message, eps,
+                                zero_grad_edge):
+    F = temp.shape[0]
+    return (temp.new_empty((t_rowptr.shape[0] - 1 if x is not None else 0, F)),
+            temp.new_empty((0 if edge is None else edge.shape[0], F)))
+
+
+def _softmax_aggr_raw(g, x, edge, temp, edge_order, message, eps, exact, stats_cols=0):
+    items, _, split, _, n_slots = g.work(exact)
+    return _timed(lambda: torch.ops.kgx.softmax_aggr(
+        x, edge, temp, g.rowptr, g.rows, items, split, g.col, n_slots,
+        g.eid if edge is not None and edge_order == "input" else None, nat.SOFTMAX_MSG[message], eps, stats_cols))
+
+
+class _SoftmaxAggrFn(torch.autograd.Function):
+    """Autograd of the fused softmax aggregation: the inputs, out and the per-row stats are kept, never an
+    [E, F] tensor; kgx_softmax_aggr_backward recomputes every weight.  d temp is one reduction over the rows,
+    sum_i grad_out (Q - out^2), from the second moment Q the forward stores when temp needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, edge, temp, g, exact, edge_order, message, eps):
+        ctx.g, ctx.exact, ctx.edge_order, ctx.message, ctx.eps = g, exact, edge_order, message, eps
+        out, stats = _softmax_aggr_raw(g, x, edge, temp, edge_order, message, eps, exact,
+                                       3 if ctx.needs_input_grad[2] else 2)
+        ctx.save_for_backward(x, edge, temp, out, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        x, edge, temp, out, stats = ctx.saved_tensors
+        g, F = ctx.g, temp.shape[0]
+        g_x = g_e = g_t = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            items, _, split, _, _ = g.work(ctx.exact)
+            by_input = ctx.edge_order == "input"
+            if x is not None:
+                t = G.transpose(g)
+                t_items, _, t_split, _, t_slots = t.work(ctx.exact)
+                t_eid = None if edge is None else (t.eid if by_input else _fwd_slot32(t))
+            else:  # by-edge messages: no source pass, the transposed graph is not built or read
+                t, t_items, t_split, t_slots, t_eid = g, None, None, 0, None
+            # input order: the rows of input edges the graph dropped belong to no slot and stay zero
+            unwritten = edge is not None and by_input and g.kept != g.n_input_edges
+            g_x, g_e = _timed(lambda: torch.ops.kgx.softmax_aggr_backward(
+                grad_out, x, edge, temp, out, stats, g.rowptr, g.rows, items, split, g.col,
+                g.eid if edge is not None and by_input else None, t.rowptr, t.rows, t_items, t_split, t.col, t_slots,
+                t_eid, nat.SOFTMAX_MSG[ctx.message], ctx.eps, unwritten))
+        if ctx.needs_input_grad[2]:
+            o = out.double()
+            g_t = (grad_out.double() * (stats[:, 2 * F:].double() - o * o)).sum(0).float()
+        return (g_x if x is not None else None), (g_e if edge is not None else None), g_t, None, None, None, None, None
+
+
+def _softmax_aggr_composed(g, x, edge, temp, edge_order, message, eps):
+    """The composed torch form (any device, any float dtype): [kept, F] messages, their segment max gathered
+    back, exponentials and products, two index_adds."""
+    from . import graph as G
+
+    dst = G.row_of_slot(g).long()
+    r = x[g.col.long()] if x is not None else None
+    if edge is not None:
+        e = edge[g.eid.long()] if edge_order == "input" else edge
+        r = e if r is None else r + e
+    m = torch.relu(r) + eps if message == "gen" else r
+    s = temp * m
+    F = m.shape[1]
+    mx = torch.full((g.n_dst, F), float("-inf"), dtype=m.dtype, device=m.device).scatter_reduce(
+        0, dst[:, None].expand(-1, F), s.detach(), "amax", include_self=True)
+    w = torch.exp(s - mx[dst])
+    zeros = torch.zeros((g.n_dst, F), dtype=m.dtype, device=m.device)
+    den = zeros.index_add(0, dst, w)
+    return zeros.index_add(0, dst, w * m) / torch.where(den > 0, den, torch.ones_like(den))
+
+
+def softmax_aggregate(
+    g: CSRGraph,
+    x: torch.Tensor | None,
+    temp=1.0,
+    *,
+    edge: torch.Tensor | None = None,
+    edge_order: str = "input",
+    message: str = "identity",
+    eps: float = 1e-7,
+    exact: bool = False,
+    fused: bool = True,
+) -> torch.Tensor:
+    """The softmax aggregation of DeeperGCN (PyG's SoftmaxAggregation; with message="gen" the aggregation of
+    GENConv), one fused pass (kgx_softmax_aggr):
+      m_e = msg(x[j] + edge[e])      out[i] = sum_{j -> i} softmax_{j -> i}(temp * m_e) * m_e     (per channel)
+    msg is the identity, or relu(.) + eps for "gen".  x [g.n_src, F], or None with edge as the per-edge messages;
+    temp a float, a 0-d tensor or [F] (0: the mean; negative: a soft minimum).  Differentiable in x, edge and
+    temp; the backward recomputes the weights, so no [E, F] tensor is written or kept in either direction.  A
+    destination without in-edges gets zeros.
+
+    edge_order="input": edge is [g.n_input_edges, F], row e the input edge e (the rows of edges the graph
+    dropped get a zero gradient); "csr": [g.kept, F] in CSR slot order.  exact: hub rows are merged whole, in
+    CSR order.
+
+    fused=False, CPU tensors, non-fp32 inputs, a graph without edges and widths outside
+    softmax_aggr_supported take the composed torch form."""
+    if edge_order not in ("input", "csr"):
+        raise ValueError(f"softmax_aggregate: edge_order must be 'input' or 'csr', got {edge_order!r}")
+    if message not in nat.SOFTMAX_MSG:
+        raise ValueError(f"softmax_aggregate: message must be 'identity' or 'gen', got {message!r}")
+    if x is None and edge is None:
+        raise ValueError("softmax_aggregate: x and edge are both None: no message")
+    if x is not None and (x.dim() != 2 or x.shape[0] != g.n_src):
+        raise ValueError(f"softmax_aggregate: x must be [{g.n_src}, F], got {tuple(x.shape)}")
+    ref = x if x is not None else edge
+    F = ref.shape[-1]
+    if edge is not None:
+        if g.flags & nat.CSR_SELF_LOOPS:
+            raise ValueError("softmax_aggregate: the graph has added self-loop slots, which carry no edge feature; "
+                             "build it without")
+        n_e = g.kept if edge_order == "csr" else g.n_input_edges
+        if tuple(edge.shape) != (n_e, F):
+            raise ValueError(f"softmax_aggregate: edge in {edge_order} order must be [{n_e}, {F}], got "
+                             f"{tuple(edge.shape)}")
+    temp = torch.as_tensor(temp, dtype=ref.dtype, device=ref.device) if not isinstance(temp, torch.Tensor) else temp
+    if temp.dim() > 1 or (temp.dim() == 1 and temp.shape[0] != F):
+        raise ValueError(f"softmax_aggregate: temp must be a scalar or [{F}], got {tuple(temp.shape)}")
+    temp = temp.expand(F)  # a scalar's gradient is summed by autograd
+    if (not fused or not ref.is_cuda or g.kept == 0 or not softmax_aggr_supported(F)
+            or any(t is not None and t.dtype != torch.float32 for t in (x, edge, temp))):
+        return _softmax_aggr_composed(g, x, edge, temp.to(ref.device), edge_order, message, eps)
+    temp = temp.to(ref.device)
+    if _needs_grad(x, edge, temp):
+        return _SoftmaxAggrFn.apply(x, edge, temp, g, exact, edge_order, message, float(eps))
+    return _softmax_aggr_raw(g, x, edge, temp, edge_order, message, float(eps), exact)[0]
