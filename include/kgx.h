@@ -1213,6 +1213,50 @@ int kgx_rgcn_workspace_bytes(int64_t n_pieces, int64_t n_split_pieces, int64_t R
 int kgx_rgcn_run(const kgx_rgcn_args* a, kgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * NNConv / ECConv: edge-conditioned aggregate and transform in one pass
+ * (nnconv.hip; no reference counterpart, PyG's NNConv with aggr "add" or "mean"
+ * and an edge network whose last layer is linear, Theta(e) = W_bias + sum_d
+ * coef[e, d] W[d]).  Over a plain CSR (rowptr [n_rows + 1], col [slots]):
+ *   S[i, d] = sum over the slots t of row i of coef[e_t, d] * x[col[t]]      d < D
+ *   S[i, D] = sum over the slots t of row i of x[col[t]]       (W_bias given)
+ *   out[i]  = bias + xroot[i] W_root + norm[i] (sum_d S[i, d] W[d] + S[i, D] W_bias)
+ *   norm    = 1 / (slots of the row) with mean (an empty row adds 0), else 1
+ * e_t = e_idx[t], or t itself when e_idx is NULL; coef [n_e, ld_coef >= D] is fp32
+ * (no alignment is asked of it) and a row outside [0, n_e) counts as 0, as does
+ * a source outside [0, n_src).  W [D, F_in, F_out], W_bias and W_root
+ * [F_in, F_out] are contiguous; W_bias, W_root and bias may be NULL (W_root
+ * given: xroot [n_rows, F_in] is required).  F_in a multiple of 4 in [4, 128],
+ * F_out a multiple of 4 in [4, 256], D in [1, 32]; x, xroot, out and bias 16-byte
+ * aligned, ld_x, ld_xroot and ld_out multiples of 4 (else KGX_ERR_UNSUPPORTED,
+ * before any device work).  The products run on bf16 MFMA with both operands
+ * split three ways (f32-accurate).  No atomics: the same bits from run to run.
+ *   struct_size   sizeof of the struct, else KGX_ERR_ARG.
+ *   pieces        int32 [n_pieces][3] = (node, slot_begin, slot_end), as in
+ *       kgx_rgcn_args: every node's slots as one piece, or cut into consecutive
+ *       ones that follow each other in the list; the pieces of cut nodes are the
+ *       first n_split_pieces.  Every node has a piece, which writes its row.
+ *   workspace     kgx_nnconv_workspace_bytes(...) bytes, 16-byte aligned: the
+ *       split weight fragments and one partial row per piece of a cut node.
+ * KGX_ERR_ARG with a message: a leading dimension below the width or >= 2^31,
+ * a null operand, a workspace that is too small.  n_rows == 0: KGX_OK.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_nnconv_args {
+  uint64_t struct_size;
+  const int32_t* rowptr; const int32_t* col; const int32_t* e_idx; const int32_t* pieces;
+  int64_t n_pieces; int64_t n_split_pieces; int64_t n_rows; int64_t n_src;
+  const float* x; int64_t ld_x; int64_t F_in;
+  const float* coef; int64_t ld_coef; int64_t n_e; int64_t D;
+  const float* W; const float* W_bias; const float* W_root; const float* bias; int64_t F_out;
+  const float* xroot; int64_t ld_xroot;
+  int32_t mean; int32_t pad_;
+  float* out; int64_t ld_out;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_nnconv_args;
+int kgx_nnconv_workspace_bytes(int64_t n_pieces, int64_t n_split_pieces, int64_t D, int64_t F_in, int64_t F_out,
+                               size_t* bytes);
+int kgx_nnconv_run(const kgx_nnconv_args* a, kgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * GAT: scalar-score graph attention (gat.hip; no reference counterpart, PyG's
  * GATConv).  The score is a sum of per-node and per-edge scalars per head:
  *   z_e = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h]      s_e = leaky_relu(z_e)

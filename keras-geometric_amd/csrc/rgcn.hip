@@ -8,7 +8,7 @@
 // changes with the relation, so the roles are turned round: the ACCUMULATORS stay
 // in registers for the whole tile and the operands stream past them.
 //
-//   * rgcn_prep_kernel splits W [R, F_in, F_out] and W_root once per call into three
+//   * wfrag::prep_kernel (kgx_wfrag.h) splits W [R, F_in, F_out] and W_root once per call into three
 //     bf16 planes (kgx_bf16x3.h, split3_a) stored in MFMA fragment order: fragment
 //     (r, kc, cb, plane) is 64 lanes x 16 bytes, lane (m, q) holding column 16 cb + m,
 //     k = 32 kc + 8 q .. + 7.  Every tile reads ready fragments (L2) and never splits W.
@@ -27,7 +27,7 @@
 //     registers across all relations; a 16-piece block with no slot of r is skipped.
 //     The root term is relation R: xroot rows against W_root.  A whole-node piece adds
 //     bias and stores its row; a piece of a split node stores a partial row (root and
-//     bias in the node's first piece) and rgcn_fixup_kernel adds a node's partials in
+//     bias in the node's first piece) and wfrag::fixup_kernel adds a node's partials in
 //     piece order.  No atomics: one writer per element, the same bits from run to run.
 #include <hip/hip_runtime.h>
 
@@ -40,17 +40,18 @@
 #include "kgx_bf16x3.h"
 #include "kgx_internal.h"
 #include "kgx_mfma.h"
+#include "kgx_wfrag.h"
 
 namespace kgx {
 namespace {
+
+using namespace wfrag;  // Planes, mfma6, split4, the prep and fix-up kernels (shared with nnconv.hip)
 
 constexpr int kM = 64;        // pieces per tile: one per lane of a wave (the tile mask is one ballot)
 constexpr int kRB = kM / 16;  // 16-piece MFMA row blocks
 constexpr int kWaves = kBlock / 64;
 constexpr int kU = 4;         // gathered rows in flight per lane group
 constexpr int kPadK = 8;      // bf16 of padding per A-tile row: 16 rows of a fragment read fall on 64 banks
-constexpr int kFrag = 512;    // bf16 per fragment plane (64 lanes x 8)
-constexpr int kFixB = 8;      // partial rows loaded together by the fix-up
 constexpr int kMaxFin = 128, kMaxFout = 256;
 
 struct TileArgs {
@@ -69,66 +70,6 @@ struct TileArgs {
   uint32_t ld_o;
   float* part;  // [n_split][F_out]
 };
-
-struct Planes {
-  bf16x8_t h, m, l;
-};
-
-__device__ __forceinline__ Planes split8(const float (&v)[8]) {
-  uint32_t h[4], m[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) split3_pair(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
-  Planes p;
-  p.h = __builtin_bit_cast(bf16x8_t, (u32x4_t{h[0], h[1], h[2], h[3]}));
-  p.m = __builtin_bit_cast(bf16x8_t, (u32x4_t{m[0], m[1], m[2], m[3]}));
-  p.l = __builtin_bit_cast(bf16x8_t, (u32x4_t{l[0], l[1], l[2], l[3]}));
-  return p;
-}
-
-// the six significant products, small terms first; W (split3_a) is the A operand, the sums (split3_a_lo on
-// the rare path: a non-finite value sits in the lo plane) the B operand, so lo meets only W's hi plane
-__device__ __forceinline__ f32x4_t mfma6(const Planes& W, const Planes& S, f32x4_t d) {
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.h, S.l, d, 0, 0, 0);
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.l, S.h, d, 0, 0, 0);
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.m, S.m, d, 0, 0, 0);
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.h, S.m, d, 0, 0, 0);
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.m, S.h, d, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(W.h, S.h, d, 0, 0, 0);
-}
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ bf16x8_t ld8(const short* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-
-struct PrepArgs {
-  const float* W;       // [R][F_in][F_out], contiguous
-  const float* W_root;  // [F_in][F_out] or null (its fragments are then never read)
-  int R, F_in, F_out, KC, NCB;
-  short* wf;
-};
-
-// One thread per (relation, k chunk, column block, lane): its 8 weights, split, 16 bytes into each plane.
-__global__ __launch_bounds__(kBlock) void rgcn_prep_kernel(PrepArgs a) {
-  const int64_t idx = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  const int64_t n_frag = int64_t(a.R + 1) * a.KC * a.NCB;
-  const int64_t frag = idx >> 6;
-  if (frag >= n_frag) return;
-  const int lane = int(idx & 63), m = lane & 15, q = lane >> 4;
-  const int cb = int(frag % a.NCB), kc = int((frag / a.NCB) % a.KC), r = int(frag / (int64_t(a.NCB) * a.KC));
-  const float* W = r < a.R ? a.W + int64_t(r) * a.F_in * a.F_out : a.W_root;
-  if (!W) return;
-  const int c = cb * 16 + m;
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int k = kc * 32 + 8 * q + i;
-    v[i] = (c < a.F_out && k < a.F_in) ? W[int64_t(k) * a.F_out + c] : 0.0f;
-  }
-  const Planes p = split8(v);
-  short* f = a.wf + frag * 3 * kFrag + lane * 8;
-  *reinterpret_cast<bf16x8_t*>(f) = p.h;
-  *reinterpret_cast<bf16x8_t*>(f + kFrag) = p.m;
-  *reinterpret_cast<bf16x8_t*>(f + 2 * kFrag) = p.l;
-}
 
 // The sum of one piece's slots [s, h) of the current relation, in CSR order, for this lane's four columns.
 // The loop count is wave-uniform (the longest of the wave's groups); a group past its end, and a lane past
@@ -161,25 +102,6 @@ __device__ __forceinline__ float4 gather_sum(const TileArgs& a, int32_t s, int32
       s += kU;
     }
     return sum;
-  }
-}
-
-// four sums -> three packed planes (two words each); the fast split unless a value is non-finite or huge
-__device__ __forceinline__ void split4(float4 s, uint32_t (&h)[2], uint32_t (&m)[2], uint32_t (&l)[2]) {
-  if (split_fast_ok(s.x, s.y, s.z, s.w)) {
-    split3_pair(s.x, s.y, h[0], m[0], l[0]);
-    split3_pair(s.z, s.w, h[1], m[1], l[1]);
-  } else {
-    const float v[4] = {s.x, s.y, s.z, s.w};
-    short hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split3_a_lo(v[i], hh[i], mm[i], ll[i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      h[i] = uint32_t(uint16_t(hh[2 * i])) | (uint32_t(uint16_t(hh[2 * i + 1])) << 16);
-      m[i] = uint32_t(uint16_t(mm[2 * i])) | (uint32_t(uint16_t(mm[2 * i + 1])) << 16);
-      l[i] = uint32_t(uint16_t(ll[2 * i])) | (uint32_t(uint16_t(ll[2 * i + 1])) << 16);
-    }
   }
 }
 
@@ -304,53 +226,15 @@ __global__ __launch_bounds__(kBlock, 3) void rgcn_tile_kernel(TileArgs a) {
   }
 }
 
-// A wave per split piece that is its node's first: the node's partial rows, added in piece order.
-__global__ __launch_bounds__(kBlock) void rgcn_fixup_kernel(const int32_t* pieces, int64_t n_split, int F_out,
-                                                            const float* part, float* out, uint32_t ld_o) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6, n_waves = (int64_t(gridDim.x) * kBlock) >> 6;
-  for (int64_t p = wid; p < n_split; p += n_waves) {  // wave-uniform
-    const int32_t node = pieces[p * 3];
-    if (p > 0 && pieces[(p - 1) * 3] == node) continue;
-    int64_t k = 1;
-    while (p + k < n_split && pieces[(p + k) * 3] == node) ++k;
-    for (int c = 4 * lane; c < F_out; c += 256) {
-      float4 s = ld4(part + p * F_out + c);
-      for (int64_t k0 = 1; k0 < k; k0 += kFixB) {
-        float4 v[kFixB];
-#pragma unroll
-        for (int u = 0; u < kFixB; ++u) {  // clamped, unconditional: all in flight together
-          const int64_t t = k0 + u < k ? k0 + u : k - 1;
-          v[u] = ld4(part + (p + t) * F_out + c);
-        }
-#pragma unroll
-        for (int u = 0; u < kFixB; ++u) {
-          const bool ok = k0 + u < k;
-          s.x = ok ? __fadd_rn(s.x, v[u].x) : s.x;
-          s.y = ok ? __fadd_rn(s.y, v[u].y) : s.y;
-          s.z = ok ? __fadd_rn(s.z, v[u].z) : s.z;
-          s.w = ok ? __fadd_rn(s.w, v[u].w) : s.w;
-        }
-      }
-      *reinterpret_cast<float4*>(out + row_off(node, ld_o) + c) = s;
-    }
-  }
-}
-
 constexpr int64_t kInt32Limit = int64_t(1) << 31;
 
-int k_chunks(int64_t F_in) { return int((F_in + 31) / 32); }
-int col_blocks(int64_t F_out) { return int((F_out + 15) / 16); }
-size_t frag_bytes(int64_t R, int64_t F_in, int64_t F_out) {
-  return align_up(size_t(R + 1) * k_chunks(F_in) * col_blocks(F_out) * 3 * kFrag * sizeof(short), 256);
-}
+size_t rgcn_frag_bytes(int64_t R, int64_t F_in, int64_t F_out) { return frag_bytes(R + 1, F_in, F_out); }
 size_t workspace_bytes(int64_t n_split, int64_t R, int64_t F_in, int64_t F_out) {
-  return frag_bytes(R, F_in, F_out) + align_up(size_t(n_split) * size_t(F_out) * sizeof(float), 256);
+  return rgcn_frag_bytes(R, F_in, F_out) + align_up(size_t(n_split) * size_t(F_out) * sizeof(float), 256);
 }
 bool shape_ok(int64_t F_in, int64_t F_out) {
   return F_in >= 4 && F_in <= kMaxFin && F_in % 4 == 0 && F_out >= 4 && F_out <= kMaxFout && F_out % 4 == 0;
 }
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 template <int NCBW>
 int launch_tiles(const TileArgs& a, hipStream_t s) {
@@ -413,18 +297,16 @@ extern "C" int kgx_rgcn_run(const kgx_rgcn_args* p, kgx_stream_t stream_) {
   hipStream_t stream = as_stream(stream_);
 
   PrepArgs w{};
-  w.W = p->W, w.W_root = p->W_root, w.R = int(p->R), w.F_in = int(p->F_in), w.F_out = int(p->F_out);
+  w.W = p->W, w.extra[0] = p->W_root, w.n_extra = 1, w.R = int(p->R), w.F_in = int(p->F_in), w.F_out = int(p->F_out);
   w.KC = k_chunks(p->F_in), w.NCB = col_blocks(p->F_out), w.wf = static_cast<short*>(p->workspace);
-  const int64_t prep_threads = int64_t(w.R + 1) * w.KC * w.NCB * 64;
-  hipLaunchKernelGGL(rgcn_prep_kernel, dim3(unsigned((prep_threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, w);
-  KGX_CHECK_LAUNCH();
+  if (const int prc = launch_prep(w, stream); prc != KGX_OK) return prc;
 
   TileArgs a{};
   a.rowptr = p->rowptr, a.col = p->col, a.pieces = p->pieces, a.n_pieces = p->n_pieces, a.n_split = p->n_split_pieces;
   a.R = w.R, a.F_in = w.F_in, a.F_out = w.F_out, a.KC = w.KC, a.NCB = w.NCB, a.mean = p->mean != 0;
   a.x = p->x, a.ld_x = uint32_t(p->ld_x), a.xroot = p->W_root ? p->xroot : nullptr, a.ld_r = uint32_t(p->ld_xroot);
   a.wf = w.wf, a.bias = p->bias, a.out = p->out, a.ld_o = uint32_t(p->ld_out);
-  a.part = reinterpret_cast<float*>(static_cast<char*>(p->workspace) + frag_bytes(p->R, p->F_in, p->F_out));
+  a.part = reinterpret_cast<float*>(static_cast<char*>(p->workspace) + rgcn_frag_bytes(p->R, p->F_in, p->F_out));
   int rc;
   if (a.NCB <= kWaves)
     rc = launch_tiles<1>(a, stream);
@@ -433,11 +315,7 @@ extern "C" int kgx_rgcn_run(const kgx_rgcn_args* p, kgx_stream_t stream_) {
   else
     rc = launch_tiles<4>(a, stream);
   if (rc != KGX_OK) return rc;
-  if (a.n_split > 0) {
-    hipLaunchKernelGGL(rgcn_fixup_kernel, dim3(grid_for(a.n_split * 64)), dim3(kBlock), 0, stream, a.pieces, a.n_split,
-                       a.F_out, a.part, a.out, a.ld_o);
-    KGX_CHECK_LAUNCH();
-  }
+  if (a.n_split > 0) return launch_fixup(a.pieces, a.n_split, a.F_out, a.part, a.out, a.ld_o, stream);
   return KGX_OK;
 }
 

@@ -23,6 +23,8 @@ from .layers import (
     PNAConv,
     ResGatedGraphConv,
     RGCNConv,
+    NNConv,
+    ECConv,
     SAGEConv,
     Set2Set,
     TransformerConv,
@@ -54,6 +56,8 @@ __all__ = [
     "NeighborSampler",
     "PNAConv",
     "RGCNConv",
+    "NNConv",
+    "ECConv",
     "ResGatedGraphConv",
     "SAGEConv",
     "SampledBlocks",

@@ -120,6 +120,21 @@ class RgcnArgs(ctypes.Structure):
     ]
 
 
+class NnconvArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("rowptr", _i32p), ("col", _i32p), ("e_idx", _i32p), ("pieces", _i32p),
+        ("n_pieces", _i64), ("n_split_pieces", _i64), ("n_rows", _i64), ("n_src", _i64),
+        ("x", _f32p), ("ld_x", _i64), ("F_in", _i64),
+        ("coef", _f32p), ("ld_coef", _i64), ("n_e", _i64), ("D", _i64),
+        ("W", _f32p), ("W_bias", _f32p), ("W_root", _f32p), ("bias", _f32p), ("F_out", _i64),
+        ("xroot", _f32p), ("ld_xroot", _i64),
+        ("mean", ctypes.c_int32), ("pad_", ctypes.c_int32),
+        ("out", _f32p), ("ld_out", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class GatArgs(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint64),
@@ -396,6 +411,8 @@ _SIGNATURES = {
     "kgx_gine_backward_run": [ctypes.POINTER(GineBackwardArgs), ctypes.c_void_p],
     "kgx_rgcn_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_rgcn_run": [ctypes.POINTER(RgcnArgs), ctypes.c_void_p],
+    "kgx_nnconv_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_nnconv_run": [ctypes.POINTER(NnconvArgs), ctypes.c_void_p],
     "kgx_gat": [ctypes.POINTER(GatArgs), ctypes.c_void_p],
     "kgx_gat_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_gat_backward": [ctypes.POINTER(GatBackwardArgs), ctypes.c_void_p],

@@ -626,3 +626,26 @@ def build_relation_csr(src: torch.Tensor, dst: torch.Tensor, edge_type: torch.Te
     pieces, n_split = relation_pieces(g.rowptr, n_dst, R, piece_len)
     return RelationGraph(graph=g, num_relations=R, n_src=n_src, n_dst=n_dst, pieces=pieces,
                          n_pieces=int(pieces.shape[0]), n_split_pieces=n_split, piece_len=piece_len)
+
+
+# ---------------------------------------------------------------------------
+# Plain CSR: the pieces list of kgx_nnconv_run
+# ---------------------------------------------------------------------------
+# A node is never cut below the hub threshold of the R-GCN path: the same walk (one lane group, one slot
+# after the other) sets the length of the heaviest tile.
+NNCONV_PIECE_LEN = RGCN_PIECE_LEN
+
+
+def csr_pieces(g: CSRGraph, *, piece_len: int | None = NNCONV_PIECE_LEN) -> tuple[torch.Tensor, int]:
+    """(pieces, n_split_pieces) of a plain CSRGraph for kgx_nnconv_run (kgx.h): int32 [n_pieces, 3] =
+    (node, slot_begin, slot_end), nodes by degree descending, a node of more than piece_len slots cut
+    every piece_len slots with its pieces first in the list; piece_len=None cuts no node.  Cached on the
+    graph per piece_len (a graph's transpose is cached on it and keeps its own)."""
+    if piece_len is not None and int(piece_len) < 1:
+        raise ValueError(f"csr_pieces: piece_len must be positive or None, got {piece_len}")
+    key = ("pieces", None if piece_len is None else int(piece_len))
+    hit = g.extras.get(key)
+    if hit is None:
+        hit = relation_pieces(g.rowptr, g.n_dst, 1, max(g.max_degree, 1) if piece_len is None else int(piece_len))
+        g.extras[key] = hit
+    return hit

@@ -25,6 +25,7 @@ from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
 from .resgated_conv import ResGatedGraphConv
+from .nn_conv import ECConv, NNConv
 from .rgcn_conv import RGCNConv
 from .sage_conv import SAGEConv
 from .transformer_conv import TransformerConv
@@ -51,6 +52,8 @@ __all__ = [
     "MultiAggregator",
     "PNAConv",
     "RGCNConv",
+    "NNConv",
+    "ECConv",
     "PoolingAggregator",
     "ResGatedGraphConv",
     "SAGEConv",

@@ -24,7 +24,7 @@ from typing import List, Optional
 import torch
 
 from . import _native as nat
-from .graph import CSRGraph
+from .graph import NNCONV_PIECE_LEN, CSRGraph
 
 
 def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -2885,6 +2885,225 @@ def rgcn_aggregate(rg, x: torch.Tensor, weight: torch.Tensor, root: torch.Tensor
         return _RgcnFn.apply(x, weight, root, bias, rg, aggr == "mean")
     out = torch.empty((rg.n_dst, F_out), dtype=torch.float32, device=x.device)
     return _timed(lambda: rgcn_into(out, rg, x, weight, root, bias, mean=aggr == "mean"))
+
+
+# ---------------------------------------------------------------------------
+# NNConv / ECConv: edge-conditioned aggregate and transform (kgx_nnconv_run)
+# ---------------------------------------------------------------------------
+def nnconv_supported(F_in: int, F_out: int, D: int) -> bool:
+    """Shapes nnconv.hip implements: multiples of 4, F_in in [4, 128], F_out in [4, 256]; D in [1, 32]."""
+    return F_in % 4 == 0 and 4 <= F_in <= 128 and F_out % 4 == 0 and 4 <= F_out <= 256 and 1 <= D <= 32
+
+
+def _nnconv_coef(coef: torch.Tensor) -> torch.Tensor:
+    if coef.dtype != torch.float32:
+        raise TypeError(f"kgx kernels compute in fp32; got {coef.dtype}")
+    if (coef.shape[1] > 1 and coef.stride(1) != 1) or (coef.shape[0] > 1 and coef.stride(0) < coef.shape[1]):
+        return coef.contiguous()
+    return coef
+
+
+def _nnconv_launch(out, g, pieces, n_split, x, coef, e_idx, weight, weight_bias, root, bias, mean):
+    D, F_in, F_out = weight.shape
+    x = _gine_table(x, F_in, "x", True)
+    if tuple(out.shape) != (g.n_dst, F_out) or out.dtype != torch.float32 or _gine_table(out, F_out, "out", True) is not out:
+        raise ValueError(f"nnconv: out must be fp32 [{g.n_dst}, {F_out}] with unit column stride and 16-byte aligned rows")
+    coef = _nnconv_coef(coef)
+    weight, weight_bias, root, bias = _f32c(weight), _f32c(weight_bias), _f32c(root), _f32c(bias)
+    dev = nat.require_device(x, out, coef, e_idx, weight, weight_bias, root, bias, g.rowptr, g.col, pieces)
+    n = ctypes.c_size_t(0)
+    nat.check(nat.lib().kgx_nnconv_workspace_bytes(pieces.shape[0], n_split, D, F_in, F_out, ctypes.byref(n)),
+              "kgx_nnconv_workspace_bytes")
+    ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+    a = nat.NnconvArgs(
+        struct_size=ctypes.sizeof(nat.NnconvArgs), rowptr=nat.addr(g.rowptr), col=nat.addr(g.col), e_idx=nat.addr(e_idx),
+        pieces=nat.addr(pieces), n_pieces=pieces.shape[0], n_split_pieces=n_split, n_rows=g.n_dst, n_src=g.n_src,
+        x=nat.addr(x), ld_x=_attn_ld(x), F_in=F_in, coef=nat.addr(coef), ld_coef=_ld(coef), n_e=coef.shape[0], D=D,
+        W=nat.addr(weight), W_bias=nat.addr(weight_bias), W_root=nat.addr(root), bias=nat.addr(bias), F_out=F_out,
+        xroot=nat.addr(x), ld_xroot=_attn_ld(x), mean=int(mean), out=nat.addr(out), ld_out=_attn_ld(out),
+        workspace=nat.addr(ws), workspace_bytes=ws.numel(),
+    )
+    nat.check(nat.lib().kgx_nnconv_run(ctypes.byref(a), nat.stream(dev)), "kgx_nnconv_run")
+    return out
+
+
+def nnconv_into(out: torch.Tensor, g: CSRGraph, x: torch.Tensor, coef: torch.Tensor, weight: torch.Tensor,
+                weight_bias: torch.Tensor | None = None, root: torch.Tensor | None = None,
+                bias: torch.Tensor | None = None, *, mean: bool = False, edge_order: str = "input",
+                piece_len: int | None = NNCONV_PIECE_LEN) -> torch.Tensor:
+    """The fused kernel writing `out` [n_dst, F_out] in place; x and out may be column-slice views of
+    wider tensors (unit column stride, 16-byte aligned rows).  coef [n_e, D] in input-edge order
+    (edge_order="input") or CSR slot order ("csr").  piece_len: graph.csr_pieces's.  No autograd."""
+    from . import graph as G
+
+    _nnconv_check(g, x, coef, weight, weight_bias, root, bias, "mean" if mean else "sum", edge_order)
+    pieces, n_split = G.csr_pieces(g, piece_len=piece_len)
+    return _nnconv_launch(out, g, pieces, n_split, x, coef, g.eid if edge_order == "input" else None, weight,
+                          weight_bias, root, bias, mean)
+
+
+def _nnconv_check(g, x, coef, weight, weight_bias, root, bias, aggr, edge_order):
+    if aggr not in ("mean", "sum"):
+        raise ValueError(f"nnconv: aggr must be 'sum' or 'mean', got {aggr!r} (the aggregate-first kernel serves "
+                         "linear reductions only)")
+    if edge_order not in ("input", "csr"):
+        raise ValueError(f"nnconv: edge_order must be 'input' or 'csr', got {edge_order!r}")
+    if g.flags & nat.CSR_SELF_LOOPS:
+        raise ValueError("nnconv: the graph has added self-loop slots, which carry no edge coefficients; build it without")
+    if x.dim() != 2 or x.shape[0] != g.n_src:
+        raise ValueError(f"nnconv: x must be [{g.n_src}, F_in], got {tuple(x.shape)}")
+    F_in = x.shape[1]
+    if weight.dim() != 3 or weight.shape[0] < 1 or weight.shape[1] != F_in:
+        raise ValueError(f"nnconv: weight must be [D, {F_in}, F_out], got {tuple(weight.shape)}")
+    D, _, F_out = weight.shape
+    rows = g.kept if edge_order == "csr" else g.n_input_edges
+    if coef.dim() != 2 or tuple(coef.shape) != (rows, D):
+        raise ValueError(f"nnconv: coef in {edge_order} order must be [{rows}, {D}] (one row per edge), got "
+                         f"{tuple(coef.shape)}")
+    if weight_bias is not None and tuple(weight_bias.shape) != (F_in, F_out):
+        raise ValueError(f"nnconv: weight_bias must be [{F_in}, {F_out}], got {tuple(weight_bias.shape)}")
+    if root is not None and (tuple(root.shape) != (F_in, F_out) or g.n_src < g.n_dst):
+        raise ValueError(f"nnconv: root must be [{F_in}, {F_out}] and the root term reads x[:n_dst], got "
+                         f"{tuple(root.shape)} with n_src = {g.n_src}, n_dst = {g.n_dst}")
+    if bias is not None and tuple(bias.shape) != (F_out,):
+        raise ValueError(f"nnconv: bias must be [{F_out}], got {tuple(bias.shape)}")
+    return F_in, F_out, D
+
+
+def _nnconv_inv_deg(g):
+    return (1.0 / g.deg.clamp(min=1).to(torch.float32)).unsqueeze(1)
+
+
+def _nnconv_sum(g, x):
+    return _aggregate_raw(g, x, nat.SUM, False, False, nat.EPI_NONE, None, None, 1.0, False)
+
+
+def _nnconv_mm(a, b):
+    return dense(a, b) if a.shape[0] else a.new_zeros((0, b.shape[1]))
+
+
+def _nnconv_composed_forward(g, x, cs, weight, weight_bias, root, bias, mean):
+    """Plane by plane: one coefficient-weighted kgx_spmm sum into an [n_dst, F_in] scratch, one kgx_dense
+    product against W_d.  cs: the coefficients in CSR slot order."""
+    x = x.contiguous()
+    out = torch.zeros((g.n_dst, weight.shape[2]), dtype=torch.float32, device=x.device)
+    for d in range(weight.shape[0]):
+        out += _nnconv_mm(_weighted_sum(g, x, cs[:, d].contiguous()), weight[d])
+    if weight_bias is not None:
+        out += _nnconv_mm(_nnconv_sum(g, x), weight_bias)
+    if mean:
+        out *= _nnconv_inv_deg(g)
+    if root is not None:
+        out += dense(x[: g.n_dst], root, bias)
+    elif bias is not None:
+        out += bias
+    return out
+
+
+def _nnconv_forward(g, x, coef, weight, weight_bias, root, bias, mean, by_input, fused, piece_len):
+    from . import graph as G
+
+    if fused:
+        out = torch.empty((g.n_dst, weight.shape[2]), dtype=torch.float32, device=x.device)
+        pieces, n_split = G.csr_pieces(g, piece_len=piece_len)
+        return _timed(lambda: _nnconv_launch(out, g, pieces, n_split, x, coef, g.eid if by_input else None, weight,
+                                             weight_bias, root, bias, mean))
+    cs = coef[g.eid.long()] if by_input else coef
+    return _nnconv_composed_forward(g, x, cs, weight, weight_bias, root, bias, mean)
+
+
+class _NnconvFn(torch.autograd.Function):
+    """Fused or composed forward; the backward keeps nothing but the inputs and is deterministic: d x is
+    the same fused kernel over the transposed graph with transposed weights (plane by plane where that
+    launch is outside the kernel's limits), d coef one kgx_edge_dot per plane, d W one weighted kgx_spmm
+    sum and one kgx_gemm_tn per plane."""
+
+    @staticmethod
+    def forward(ctx, x, coef, weight, weight_bias, root, bias, g, mean, by_input, fused, piece_len):
+        ctx.g, ctx.mean, ctx.by_input, ctx.fused, ctx.piece_len = g, mean, by_input, fused, piece_len
+        ctx.save_for_backward(x, coef, weight, weight_bias, root, bias)
+        return _nnconv_forward(g, x, coef, weight, weight_bias, root, bias, mean, by_input, fused, piece_len)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import graph as G
+
+        x, coef, weight, weight_bias, root, bias = ctx.saved_tensors
+        g, by_input = ctx.g, ctx.by_input
+        D, F_in, F_out = weight.shape
+        need = ctx.needs_input_grad
+        gout = grad_out.contiguous()
+        gs = gout * _nnconv_inv_deg(g) if ctx.mean else gout  # g': the rows scaled by norm_i
+        xc = x.contiguous()
+        g_x = g_c = g_w = g_wb = g_root = g_b = None
+        if need[0]:
+            t = G.transpose(g)
+            if ctx.fused and nnconv_supported(F_out, F_in, D):
+                g_x = torch.empty((g.n_src, F_in), dtype=torch.float32, device=x.device)
+                pieces, n_split = G.csr_pieces(t, piece_len=ctx.piece_len)
+                wt = weight.transpose(1, 2).contiguous()
+                wbt = None if weight_bias is None else weight_bias.t().contiguous()
+                e_idx = t.eid if by_input else _fwd_slot32(t)
+                _timed(lambda: _nnconv_launch(g_x, t, pieces, n_split, gs, coef, e_idx, wt, wbt, None, None, False))
+            else:
+                ct = coef[(t.eid if by_input else _fwd_slot32(t)).long()]
+                g_x = torch.zeros((g.n_src, F_in), dtype=torch.float32, device=x.device)
+                for d in range(D):
+                    g_x += _weighted_sum(t, _matmul_t(gs, weight[d]), ct[:, d].contiguous())
+                if weight_bias is not None:
+                    g_x += _nnconv_sum(t, _matmul_t(gs, weight_bias))
+            if root is not None:
+                g_x[: g.n_dst] += _matmul_t(gout, root)
+        if need[1]:  # d coef[e, d] = <g'[dst_e] W_d^T, x[src_e]>
+            g_cs = torch.zeros((g.kept, D), dtype=torch.float32, device=x.device)
+            if g.kept:
+                bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+                row, colk = G.row_of_slot(g), g.col.reshape(-1, 1)
+                for d in range(D):
+                    T = _matmul_t(gs, weight[d])
+                    g_cs[:, d] = _timed(lambda: torch.ops.kgx.edge_dot(T, xc, row, colk, None, bad)).reshape(-1)
+            g_c = g_cs
+            if by_input:  # rows of input edges the graph dropped belong to no slot and stay zero
+                g_c = torch.zeros_like(coef).index_copy_(0, g.eid.long(), g_cs)
+        if need[2]:
+            cs = coef[g.eid.long()] if by_input else coef
+            g_w = torch.empty_like(weight)
+            for d in range(D):
+                g_w[d] = gemm_tn(_weighted_sum(g, xc, cs[:, d].contiguous()), gs)[0]
+        if weight_bias is not None and need[3]:
+            g_wb = gemm_tn(_nnconv_sum(g, xc), gs)[0]
+        want_b = bias is not None and need[5]
+        if root is not None and need[4]:
+            g_root, g_b = gemm_tn(x[: g.n_dst], gout, with_db=want_b)
+        elif want_b:
+            g_b = gout.sum(0)
+        return g_x, g_c, g_w, g_wb, g_root, g_b, None, None, None, None, None
+
+
+def nnconv_aggregate(g: CSRGraph, x: torch.Tensor, coef: torch.Tensor, weight: torch.Tensor,
+                     weight_bias: torch.Tensor | None = None, root: torch.Tensor | None = None,
+                     bias: torch.Tensor | None = None, *, aggr: str = "sum", fused: bool | None = None,
+                     edge_order: str = "input", piece_len: int | None = NNCONV_PIECE_LEN) -> torch.Tensor:
+    """The edge-conditioned convolution (PyG's NNConv / ECConv) for an edge network that ends in a linear
+    layer, Theta(e) = weight_bias + sum_d coef[e, d] * weight[d]:
+        out[i] = bias + x[i] @ root + aggr_{j -> i} x[j] @ Theta(e_ij)        aggr "sum" or "mean"
+    computed aggregate-first, out[i] = bias + x[i] root + norm_i (sum_d (sum_j coef[e, d] x[j]) weight[d] +
+    (sum_j x[j]) weight_bias), so nothing of size E x F_in x F_out exists.
+
+    coef [E, D]: the edge network's last hidden activation (or the raw attributes), in the caller's edge
+    order; weight [D, F_in, F_out], weight_bias and root [F_in, F_out], bias [F_out].  fused=None takes the
+    one-pass kernel (kgx_nnconv_run) on the shapes it implements (nnconv_supported) and the composed form
+    (per plane a weighted kgx_spmm sum and a kgx_dense product) elsewhere; fused=False is the composed
+    form.  piece_len: graph.csr_pieces's hub cut, for the graph and its transpose.  "max" / "min" are
+    not linear and raise ValueError.  Differentiable in x, coef, weight, weight_bias, root and bias; the
+    backward keeps only the inputs and is deterministic."""
+    F_in, F_out, D = _nnconv_check(g, x, coef, weight, weight_bias, root, bias, aggr, edge_order)
+    use = fused is not False and nnconv_supported(F_in, F_out, D)
+    mean, by_input = aggr == "mean", edge_order == "input"
+    if _needs_grad(x, coef, weight, weight_bias, root, bias):
+        return _NnconvFn.apply(x, coef, weight, weight_bias, root, bias, g, mean, by_input, use, piece_len)
+    with torch.no_grad():
+        return _nnconv_forward(g, x, coef, weight, weight_bias, root, bias, mean, by_input, use, piece_len)
 
 
 # ---------------------------------------------------------------------------
