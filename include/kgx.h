@@ -1456,6 +1456,56 @@ int kgx_softmax_aggr(const kgx_softmax_aggr_args* a, kgx_stream_t stream);
 int kgx_softmax_aggr_backward_workspace_bytes(int64_t n_rows, int64_t t_n_slots, int64_t F, size_t* bytes);
 int kgx_softmax_aggr_backward(const kgx_softmax_aggr_backward_args* a, kgx_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * k nearest neighbours within segments (knn.hip; no reference counterpart, PyG's
+ * knn / knn_graph, the graph build of DynamicEdgeConv).  For every query row
+ * y[i] of [Q, D] fp32 in segment s (seg_y[s] <= i < seg_y[s + 1]), the k rows
+ * x[c] of [P, D] fp32 with seg_x[s] <= c < seg_x[s + 1] of smallest squared
+ * distance:
+ *   nbr[i, 0..k)    int32, ascending in (computed d2, c): ties go to the lower index
+ *   dist2[i, 0..k)  fp32 d2 of those rows (NULL: not written)
+ * A query with fewer than k candidates pads nbr with -1 and dist2 with +inf.
+ * exclude_self != 0 skips candidate c == i for query i (knn_graph: y == x with
+ * equal segments): by index, never by distance, so a duplicate of a point is a
+ * valid neighbour.  A candidate whose computed d2 is NaN or +inf is never
+ * selected.  Nothing of size Q x P is written; no atomics: the output is a pure
+ * function of the inputs, the same bits from run to run.
+ *   D <= 8       acc = 0; for d ascending: t = y_d - x_d; acc = acc + t * t, every
+ *                operation a separately rounded fp32 one.
+ *   8 < D <= 256 d2 = max(0, (|y|^2 + |x|^2) - 2 c), the norms accumulated as
+ *                above (acc + x_d * x_d) and the cross term c on bf16 MFMA with
+ *                both operands split three ways (six products, f32-accurate).
+ *   struct_size  sizeof of the struct, else KGX_ERR_ARG.
+ *   seg_x, seg_y HOST arrays of S + 1 ascending offsets from 0 to P / Q (one
+ *       segment: {0, P}, {0, Q}); they are checked on the host and copied into
+ *       the workspace in ONE copy (seg_y == seg_x: of one array).  The copy is
+ *       from pageable host memory, so the call SYNCHRONISES WITH THE HOST: it
+ *       waits for the work queued on `stream`, and it cannot be recorded in a
+ *       stream capture.  The arrays may be freed when the call returns.  x, y,
+ *       nbr, dist2 and workspace are device memory; no alignment is asked of
+ *       x, y, nbr and dist2.
+ *   workspace    kgx_knn_workspace_bytes(P, Q, D, S) bytes, 16-byte aligned: the
+ *       offsets and, for D > 8, the split rows and norms of both operands.
+ * KGX_ERR_ARG with a message, before any device call: a null pointer, k outside
+ * [1, 64], D outside [1, 256], P or Q outside [0, 2^31 - 64), offsets that do not
+ * ascend from 0 to P / Q, a leading dimension below its width or >= 2^31,
+ * Q k >= 2^31, exclude_self with Q > P, a workspace that is too small.
+ * Q == 0: KGX_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+typedef struct kgx_knn_args {
+  uint64_t struct_size;
+  const float* x; int64_t ld_x; int64_t P;
+  const float* y; int64_t ld_y; int64_t Q;
+  int64_t D; int64_t k;
+  const int32_t* seg_x; const int32_t* seg_y; int64_t S;
+  int32_t exclude_self; int32_t pad_;
+  int32_t* nbr; int64_t ld_nbr;
+  float* dist2; int64_t ld_dist2;
+  void* workspace; uint64_t workspace_bytes;
+} kgx_knn_args;
+int kgx_knn_workspace_bytes(int64_t P, int64_t Q, int64_t D, int64_t S, size_t* bytes);
+int kgx_knn(const kgx_knn_args* a, kgx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ from .layers import (
     AttentionPooling,
     BatchGlobalPooling,
     DotProductDecoder,
+    DynamicEdgeConv,
+    EdgeConv,
     GATConv,
     GATv2Conv,
     GCNConv,
@@ -30,6 +32,7 @@ from .layers import (
     TransformerConv,
     set_random_seed,
 )
+from .knn import knn, knn_csr, knn_graph, knn_supported
 from .sampling import EdgeBatch, NegativeSampler, NeighborSampler, SampledBlocks, SampledSubgraph
 from .utils import GraphData, add_self_loops, batch_graphs, compute_gcn_normalization
 
@@ -42,7 +45,9 @@ __all__ = [
     "Block",
     "CSRGraph",
     "DotProductDecoder",
+    "DynamicEdgeConv",
     "EdgeBatch",
+    "EdgeConv",
     "GATConv",
     "GATv2Conv",
     "GCNConv",
@@ -70,6 +75,10 @@ __all__ = [
     "clear_cache",
     "compute_gcn_normalization",
     "graph",
+    "knn",
+    "knn_csr",
+    "knn_graph",
+    "knn_supported",
     "ops",
     "set_random_seed",
 ]

@@ -135,6 +135,20 @@ class NnconvArgs(ctypes.Structure):
     ]
 
 
+class KnnArgs(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("x", _f32p), ("ld_x", _i64), ("P", _i64),
+        ("y", _f32p), ("ld_y", _i64), ("Q", _i64),
+        ("D", _i64), ("k", _i64),
+        ("seg_x", _i32p), ("seg_y", _i32p), ("S", _i64),  # host arrays
+        ("exclude_self", ctypes.c_int32), ("pad_", ctypes.c_int32),
+        ("nbr", _i32p), ("ld_nbr", _i64),
+        ("dist2", _f32p), ("ld_dist2", _i64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class GatArgs(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint64),
@@ -413,6 +427,8 @@ _SIGNATURES = {
     "kgx_rgcn_run": [ctypes.POINTER(RgcnArgs), ctypes.c_void_p],
     "kgx_nnconv_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_nnconv_run": [ctypes.POINTER(NnconvArgs), ctypes.c_void_p],
+    "kgx_knn_workspace_bytes": [_i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_size_t)],
+    "kgx_knn": [ctypes.POINTER(KnnArgs), ctypes.c_void_p],
     "kgx_gat": [ctypes.POINTER(GatArgs), ctypes.c_void_p],
     "kgx_gat_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(ctypes.c_size_t)],
     "kgx_gat_backward": [ctypes.POINTER(GatBackwardArgs), ctypes.c_void_p],

@@ -25,6 +25,7 @@ from .message_passing import MessagePassing
 from .pna_conv import PNAConv
 from .pooling import BatchGlobalPooling, GlobalPooling
 from .resgated_conv import ResGatedGraphConv
+from .edge_conv import DynamicEdgeConv, EdgeConv
 from .nn_conv import ECConv, NNConv
 from .rgcn_conv import RGCNConv
 from .sage_conv import SAGEConv
@@ -53,6 +54,8 @@ __all__ = [
     "PNAConv",
     "RGCNConv",
     "NNConv",
+    "EdgeConv",
+    "DynamicEdgeConv",
     "ECConv",
     "PoolingAggregator",
     "ResGatedGraphConv",
